@@ -10,7 +10,15 @@ slot. One process per GPU = one agent; frames are agent-p
 per-GPU work is fixed as N grows ("weak" scaling). The B frames are split over P concurrent,
 staggered extraction+match graphs (default 3840 frames as 3 graphs of 1280).
 
-After the timed region the run checks itself: every graph's device error flags, then sampled
+A plain run does only what the headline figure needs: it sets up, runs --warmup steps, times --steps
+steps (host clock around them, `ms_per_step`), reads every graph's device error flags (exit status 3 when
+one is set), writes the last timed step's outputs with --dump-outputs DIR (dump_outputs below; the frames
+are synthetic and deterministic, so two builds compare output for output) and prints the result line.
+Everything below this paragraph runs with --full only, which adds its fields to the same line: the stage
+split, the rooflines, the oracle self-check, the extract-only / match-only passes, the ingest leg, the
+sustained pass and the CPU baseline.
+
+After the timed region a --full run checks itself: every graph's device error flags, then sampled
 frames (first / middle / last of every graph) with their match rows and the cross-agent matches,
 bit-compared against the CPU oracle (oracle/check_schedule.py, the checker); "bit_exact" in the
 JSON line, exit status 3 on a mismatch. The frames form a pool of --pool resident batches and
@@ -282,6 +290,89 @@ def run_ingest(torch, sched, frames_np, pool, nsteps, B, W, H, world, use_dist, 
                       % (pool, B, nst, k, "on the host" if host_wait else "stream wait on the copy streams")}
 
 
+DUMP_FRAMES = 16  # --dump-outputs: frames per graph written whole (a fixed, seeded sample)
+DUMP_SEED = 20
+DUMP_SAMPLE_BYTES = 48 << 20  # the sampled frames' arrays stay below this (the whole dump below 64 MB)
+
+
+def dump_outputs(torch, sched, out_dir, rank=0, world=1):
+    """--dump-outputs: the arrays the last step of the schedule left for its caller, as out_dir/<name>.npy
+    (<name>_rank<r>.npy at N > 1), graphs back to back along axis 0. Entries past a frame's keypoint count are
+    unspecified on the device and written as 0 (match rows: -1, "no match").
+    Every extraction image / frame of the step:
+      counts [images] f32, nmatch [frames] f32 (stereo: nstereo [frames] f32), and frame_sums [images, 3] f64 = the
+      sums of x, of y and of the descriptor bytes over the image's keypoints; match_sums [frames] f64 = the sum of
+      the frame's match row.
+    A fixed sample of frames per graph (sample_frames f32: frame 0, the last one and seeded picks, the same in
+    every run and graph), whole: keypoints [n, stride, 6] f32 (x, y, size, angle, response, octave), descriptors
+    [n, stride, 32] f32 (one byte each), matches [n, stride] f32; stereo: right_keypoints, right_descriptors,
+    uright, depth.
+    The exchange: xmatch / xbow [world, stride] f32 (the keyframe's SearchForTriangulation / SearchByBoW rows against
+    every agent's slot) and their counts xn / xbn [world] f32."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    P, sub, per = sched.P, sched.sub, sched.images_per_frame
+    S = sched.pipes[0].stride
+    # per keypoint slot: 6 + 32 floats per image, the match entry, stereo: uright + depth
+    frame_bytes = S * (per * (24 + 128) + 4 + (8 if per == 2 else 0))
+    ns = min(DUMP_FRAMES, sub, DUMP_SAMPLE_BYTES // (P * frame_bytes))
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = rng.choice(np.arange(1, max(sub - 1, 1)), size=max(ns - 2, 0), replace=False)
+    pick = np.unique(np.concatenate([[0, sub - 1], mid]).astype(np.int64))
+    out = {k: [] for k in ("counts", "nmatch", "frame_sums", "match_sums", "keypoints", "descriptors", "matches")}
+    if per == 2:
+        out.update({k: [] for k in ("nstereo", "right_keypoints", "right_descriptors", "uright", "depth")})
+
+    def kp_rows(pp, idx):
+        """keypoints / descriptors of extraction images idx as f32, zero past each image's count"""
+        n = pp.counts[idx].cpu().numpy()
+        k = pp.kps[idx].cpu().numpy()
+        k[..., 5] = np.ascontiguousarray(k[..., 5]).view(np.int32).astype(np.float32)  # octave: int32 bits
+        valid = np.arange(S)[None, :] < n[:, None]
+        return (np.where(valid[..., None], k, np.float32(0)),
+                np.where(valid[..., None], pp.desc[idx].cpu().numpy().astype(np.float32), np.float32(0)), valid)
+
+    for pp in sched.pipes:
+        idx = torch.from_numpy(pick).to(pp.dev)
+        cnt = pp.counts.to(torch.int64)
+        valid = torch.arange(S, device=pp.dev)[None, :] < cnt[:, None]
+        zero = torch.zeros((), dtype=torch.float64, device=pp.dev)
+        sums = [torch.where(valid, pp.kps[:, :, c].double(), zero).sum(1) for c in (0, 1)]
+        sums.append(torch.where(valid, pp.desc.sum(2, dtype=torch.int64).double(), zero).sum(1))
+        out["frame_sums"].append(torch.stack(sums, 1).cpu().numpy())
+        out["match_sums"].append(torch.where(valid[:sub], pp.match.double(), zero).sum(1).cpu().numpy())
+        out["counts"].append(pp.counts.cpu().numpy().astype(np.float32))
+        out["nmatch"].append(pp.nmatch.cpu().numpy().astype(np.float32))
+        k, d, v = kp_rows(pp, idx)
+        out["keypoints"].append(k)
+        out["descriptors"].append(d)
+        out["matches"].append(np.where(v, pp.match[idx].cpu().numpy().astype(np.float32), np.float32(-1)))
+        if per == 2:
+            out["nstereo"].append(pp.nstereo.cpu().numpy().astype(np.float32))
+            k, d, _ = kp_rows(pp, idx + sub)
+            out["right_keypoints"].append(k)
+            out["right_descriptors"].append(d)
+            out["uright"].append(np.where(v, pp.uright[idx].cpu().numpy(), np.float32(0)))
+            out["depth"].append(np.where(v, pp.depth[idx].cpu().numpy(), np.float32(0)))
+    arrays = {k: np.concatenate(v) for k, v in out.items()}
+    arrays["sample_frames"] = pick.astype(np.float32)
+    if sched.exchange_on:
+        n = int(sched.pipes[0].counts[0].item())
+        for name, t in (("xmatch", sched.xmatch), ("xbow", sched.xbow)):
+            a = t.cpu().numpy().astype(np.float32)
+            a[:, n:] = -1
+            arrays[name] = a
+        arrays["xn"] = sched.xn.cpu().numpy().astype(np.float32)
+        arrays["xbn"] = sched.xbn.cpu().numpy().astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ("" if world == 1 else "_rank%d" % rank) + ".npy"), a)
+    return total
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` called directly (no WORLD_SIZE in the environment) with N > 1: start N ranks
     under torch.distributed.run as a child process and exit with its status (rank 0 prints the JSON line
@@ -386,6 +477,15 @@ def main():
                          "first step of a run (the phase offset then persists) / never / in the first step and every "
                          "K-th step after it; pyr_ / fast_: after graph p-1's pyramid / FAST instead (a third of the step "
                          "apart at 3 graphs)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the stage split, the rooflines (priced kernels live and alone, the "
+                         "copy bandwidth), the oracle self-check, the extract-only / match-only passes, the ingest leg, "
+                         "the sustained pass and the CPU baseline (--no-check, --no-cpu, --sustain, --ingest-steps, "
+                         "--roof-kernel and the --cpu-* options act only here). Without it a run sets up, warms up, "
+                         "times --steps steps, reads the device error flags and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64; see dump_outputs)")
     ap.add_argument("--launch-frames", action="store_true",
                     help="print the images one stage launch processes (--batch / --pipes frames, x2 for stereo pairs) and "
                          "the graph count, and exit (no GPU use)")
@@ -566,29 +666,37 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
-    # 1) stage split (untimed): every stage bracketed, same schedule
-    _, stage_ms = run_profiled(0x1F, args.steps, False)
-    # the roofline kernel: the extraction stage with the largest live time in this run's own stage split (every
-    # stage bracketed by HIP events on the stream it runs on, same overlapped schedule); --roof-kernel overrides
-    ranked = sorted(stages, key=lambda k: -stage_ms[k])
-    dom = ranked[0] if args.roof_kernel == "auto" else args.roof_kernel
-    # a second stage within 5 % of the largest is priced beside it (`roofline.co_dominant`): the split's event pairs
-    # cannot rank two stages that close (round-4 review)
-    co = (ranked[1] if args.roof_kernel == "auto" and stage_ms[ranked[1]] >= 0.95 * stage_ms[dom] else None)
-    # 2) timed region: only the priced kernels bracketed (their live launch durations for the roofline)
-    el, dom_live = run_profiled((1 << stages.index(dom)) | ((1 << stages.index(co)) if co else 0), args.steps, True)
+    stage_ms = dom = co = None
+    if args.full:
+        # 1) stage split (untimed): every stage bracketed, same schedule
+        _, stage_ms = run_profiled(0x1F, args.steps, False)
+        # the roofline kernel: the extraction stage with the largest live time in this run's own stage split (every
+        # stage bracketed by HIP events on the stream it runs on, same overlapped schedule); --roof-kernel overrides
+        ranked = sorted(stages, key=lambda k: -stage_ms[k])
+        dom = ranked[0] if args.roof_kernel == "auto" else args.roof_kernel
+        # a second stage within 5 % of the largest is priced beside it (`roofline.co_dominant`): the split's event
+        # pairs cannot rank two stages that close (round-4 review)
+        co = (ranked[1] if args.roof_kernel == "auto" and stage_ms[ranked[1]] >= 0.95 * stage_ms[dom] else None)
+    # 2) timed region: --steps steps of the schedule, host clock around them. --full: the priced kernels bracketed
+    # (their live launch durations for the roofline); a plain run brackets nothing
+    mask = ((1 << stages.index(dom)) | ((1 << stages.index(co)) if co else 0)) if args.full else 0
+    sched.cursor = args.warmup  # the timed steps process the same pool batches with and without --full
+    el, dom_live = run_profiled(mask, args.steps, True)
     last_batch, prev_batch = sched.last_batch, (sched.last_batch - 1) % args.pool
     el = reduce_max(el)
-    # 3) self-check of the last timed step (error flags on every rank; oracle bit-compare of sampled frames,
-    # their match rows and the cross-agent matches)
+    # 3) the last timed step's device error flags on every rank, then its outputs (--dump-outputs), before anything
+    # else runs on the buffers; --full: the self-check (oracle bit-compare of sampled frames, their match rows and the
+    # cross-agent matches)
     err_msg = None
     try:
         sched.check_errors()
     except RuntimeError as e:
         err_msg = str(e)
+    if args.dump_outputs:
+        dump_outputs(torch, sched, args.dump_outputs, rank, world)
     check = None
     agent_kf = lambda r, t: agent_frames(r, t, 1)[0]  # noqa: E731 (agent r's keyframe image / stereo pair)
-    if not args.no_check:
+    if args.full and not args.no_check:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         from check_schedule import check_schedule
         check = check_schedule(sched, frames_np, nfeatures=cfg["nfeatures"], agent_frames=agent_kf)
@@ -596,6 +704,73 @@ def main():
     ok_all = ok_local
     if use_dist:
         ok_all = int(reduce_max(0 if ok_local else 1, torch.int32)) == 0
+    total_frames = world * B * args.steps
+    value = total_frames / el
+
+    def mean_counts():
+        """keypoints per image and matches per pair of the step that ran last, averaged over the graphs"""
+        return (float(sum(pp.counts.float().mean().item() for pp in pipes) / P),
+                float(sum(pp.nmatch.float().mean().item() for pp in pipes) / P))
+
+    def headline(nkp, nmatch):
+        """the fields of the result line that every run reports"""
+        return {
+            "metric": ("frames/sec ORB extract+match, 640x480 mono, 1000 feat/frame" if args.config == "c2" else
+                       "stereo frames/sec ORB extract(L+R)+stereo match+match, %dx%d, %d feat/image" % (W, H, cfg["nfeatures"])
+                       if rig else "frames/sec ORB extract+match, %dx%d left images, %d feat/frame"
+                       % (W, H, cfg["nfeatures"])),
+            "value": round(value, 2),
+            "unit": "stereo frames/s" if rig else "frames/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(el / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "u8",
+            "full": bool(args.full),
+            "data": "synthetic (deterministic textured pan, SURVEY.md 8(d)); resident in HBM",
+            "config": {"workload": cfg["name"] + ", scale 1.2, 8 levels, FAST 20/7; " +
+                                   ("stereo pairs (right image at disparity %d px; mbf %.4f, mb %.5f): extract left + right "
+                                    "+ ComputeStereoMatches + BF SearchForTriangulation (stereo branch)" % (cfg["dx"], rig[0], rig[1])
+                                    if rig else "extract + BF SearchForTriangulation") +
+                                   " vs previous frame + per-step keyframe BoW + slot all-gather & cross-agent "
+                                   "SearchForTriangulation and SearchByBoW(KF,KF)",
+                       "config": args.config, "stereo": bool(rig), "frames_per_step_per_gpu": B,
+                       "images_per_step_per_gpu": per * B, "graphs_per_gpu": P,
+                       "graph_stagger": args.stagger, "scene": args.scene,
+                       "exchange_stream": "own" if async_x else "graph 0's",
+                       "parallelism": "agent-per-gpu x%d" % world},
+            "device_errors": err_msg,
+            "per_gpu_frames_per_s": round(value / world, 2),
+            "kp_per_image": round(nkp, 1),
+            "matches_per_pair": round(nmatch, 1),
+            "collective": ("rccl ncclAllGather by liborbamd (orbx_comm_allgather) on %s stream, out-of-place slot "
+                           "buffer; gloo control plane" % ("the exchange's own" if async_x else "graph 0's")
+                           if use_dist and coll == "rccl" else
+                           "rccl all_gather_into_tensor (torch ProcessGroupNCCL, out-of-place slot buffer)"
+                           if use_dist and coll == "torch"
+                           else "gloo all_gather through host memory (rehearsal)" if use_dist
+                           else "none (N=1: the keyframe slot is packed in place)"),
+        }
+
+    def finish(result):
+        """rank 0 prints the result line; every rank tears down and exits 3 when a check failed"""
+        if rank == 0:
+            print(json.dumps(result), flush=True)
+        sched.close()
+        if use_dist:
+            dist.barrier()
+            if comm is not None:
+                orbamd.load().orbx_comm_destroy(comm)
+            dist.destroy_process_group()
+        if not ok_all:
+            sys.exit(3)
+
+    if not args.full:  # a plain run ends here: the headline figure alone
+        finish(headline(*mean_counts()))
+        return
     # 3b) the priced kernels alone (untimed, after the check): graph 0 re-extracts the last batch in stage order with
     # every other graph idle, one step at a time, the priced stages bracketed by HIP events; the live launch above is
     # the kernel's share of a chip running the other graphs, this is its own speed (roofline.alone)
@@ -657,11 +832,7 @@ def main():
             dist.barrier()
         sus_s = reduce_max(run_part(n_sus))
         sustained = {"seconds": round(sus_s, 3), "steps": n_sus, "frames_per_s": round(world * B * n_sus / sus_s, 1)}
-    nkp = float(sum(pp.counts.float().mean().item() for pp in pipes) / P)
-    nmatch = float(sum(pp.nmatch.float().mean().item() for pp in pipes) / P)
-
-    total_frames = world * B * args.steps
-    value = total_frames / el
+    nkp, nmatch = mean_counts()
     result = None
     if rank == 0:
         b_frame, per_stage = algorithmic_bytes(W, H, nkp)
@@ -762,38 +933,12 @@ def main():
                            "peak": VALU_PEAK_GINST, "unit": "G wave64 VALU instr/s",
                            "frac": round(step_valu / step_s / 1e9 / VALU_PEAK_GINST, 4)} if step_valu else None)
         result = {
-            "metric": ("frames/sec ORB extract+match, 640x480 mono, 1000 feat/frame" if args.config == "c2" else
-                       "stereo frames/sec ORB extract(L+R)+stereo match+match, %dx%d, %d feat/image" % (W, H, cfg["nfeatures"])
-                       if rig else "frames/sec ORB extract+match, %dx%d left images, %d feat/frame"
-                       % (W, H, cfg["nfeatures"])),
-            "value": round(value, 2),
-            "unit": "stereo frames/s" if rig else "frames/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(el / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic (deterministic textured pan, SURVEY.md 8(d)); resident in HBM",
-            "config": {"workload": cfg["name"] + ", scale 1.2, 8 levels, FAST 20/7; " +
-                                   ("stereo pairs (right image at disparity %d px; mbf %.4f, mb %.5f): extract left + right "
-                                    "+ ComputeStereoMatches + BF SearchForTriangulation (stereo branch)" % (cfg["dx"], rig[0], rig[1])
-                                    if rig else "extract + BF SearchForTriangulation") +
-                                   " vs previous frame + per-step keyframe BoW + slot all-gather & cross-agent "
-                                   "SearchForTriangulation and SearchByBoW(KF,KF)",
-                       "config": args.config, "stereo": bool(rig), "frames_per_step_per_gpu": B,
-                       "images_per_step_per_gpu": per * B, "graphs_per_gpu": P,
-                       "graph_stagger": args.stagger, "scene": args.scene,
-                       "exchange_stream": "own" if async_x else "graph 0's",
-                       "parallelism": "agent-per-gpu x%d" % world},
+            **headline(nkp, nmatch),
             "bit_exact": bool(ok_all) if check is not None else None,
             "checked_frames": check["checked_frames"] if check else 0,
             "checked_pairs": check["checked_pairs"] if check else 0,
             "checked_slots": check["checked_slots"] if check else 0,
             "slot_bow_matches": check.get("slot_bow_matches") if check else None,
-            "device_errors": err_msg,
             "roofline": roof,
             "match_roofline": {"bound": "mfma", "kernel": "k_tri_mfma", "achieved": round(m_tops, 2),
                                "peak": FP4_MFMA_PEAK_TOPS, "unit": "fp4 TOPS", "frac": round(m_tops / FP4_MFMA_PEAK_TOPS, 4),
@@ -805,11 +950,8 @@ def main():
             "pipeline_hbm": {"bytes_per_image": b_frame, "achieved_GBs": round(b_frame * per * value / world / 1e9, 2),
                              "frac": round(b_frame * per * value / world / 1e9 / HBM_PEAK_GBS, 5)},
             "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
-            "per_gpu_frames_per_s": round(value / world, 2),
             "extract_only_frames_per_s_per_gpu": round(extract_fps, 1),
             "match_only_pairs_per_s_per_gpu": round(match_pps, 1),
-            "kp_per_image": round(nkp, 1),
-            "matches_per_pair": round(nmatch, 1),
             "sustained": sustained,
             "ingest": ingest,
             "stale_guard": {"frame_pool_batches": args.pool, "checked_step_batch": last_batch,
@@ -818,13 +960,6 @@ def main():
                                     "launch in the checked (last timed) step leaves the previous batch's outputs and "
                                     "fails the oracle check" if args.pool > 1 else
                                     "pool of 1: repeated frames, a skipped launch would not be detected"},
-            "collective": ("rccl ncclAllGather by liborbamd (orbx_comm_allgather) on %s stream, out-of-place slot "
-                           "buffer; gloo control plane" % ("the exchange's own" if async_x else "graph 0's")
-                           if use_dist and coll == "rccl" else
-                           "rccl all_gather_into_tensor (torch ProcessGroupNCCL, out-of-place slot buffer)"
-                           if use_dist and coll == "torch"
-                           else "gloo all_gather through host memory (rehearsal)" if use_dist
-                           else "none (N=1: the keyframe slot is packed in place)"),
         }
         if check is not None and check["mismatches"]:
             result["mismatches"] = check["mismatches"]
@@ -862,16 +997,7 @@ def main():
         result["speedup_vs_cpu_1thread"] = round(value / fps1, 1)
     elif rank == 0:
         result["cpu_baseline"] = None
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    sched.close()
-    if use_dist:
-        dist.barrier()
-        if comm is not None:
-            orbamd.load().orbx_comm_destroy(comm)
-        dist.destroy_process_group()
-    if not ok_all:
-        sys.exit(3)
+    finish(result)
 
 
 if __name__ == "__main__":

@@ -43,6 +43,18 @@ def test_launch_frames_query():
     assert sub * pipes > 0 and sub >= 64
 
 
+def test_full_and_dump_outputs_options():
+    """--full (everything beside the headline figure) and --dump-outputs DIR are options of the parser, both off by
+    default: the help text names them, and the query that needs no GPU accepts them"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120, cwd=ROOT, env=_env())
+    assert r.returncode == 0 and "--full" in r.stdout and "--dump-outputs DIR" in r.stdout
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--dump-outputs", "unused",
+                        "--launch-frames"], capture_output=True, text=True, timeout=120, cwd=ROOT, env=_env())
+    assert r.returncode == 0 and len(r.stdout.split()) == 2, r.stderr[-2000:]
+    assert not os.path.exists(os.path.join(ROOT, "unused"))
+
+
 def test_describe_touched_bytes_is_the_patch_union():
     """describe's algorithmic bytes (bench.describe_touched_bytes): per level the union of the windows its patches
     read, at most every level pixel once, plus 56 B per keypoint; the fused form (the 43x43 unblurred source window)

@@ -299,8 +299,8 @@ def test_bench_rccl_world1(collective):
     port = _free_port()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--dist", "--steps", "4",
-           "--warmup", "2", "--batch", "256", "--pipes", "2", "--no-cpu", "--sustain", "0", "--ingest-steps", "4",
-           "--collective", collective]
+           "--warmup", "2", "--batch", "256", "--pipes", "2", "--full", "--no-cpu", "--sustain", "0",
+           "--ingest-steps", "4", "--collective", collective]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT,
                        env=dict(os.environ, MASTER_ADDR="127.0.0.1"))
     print(r.stdout[-3000:], r.stderr[-3000:])
@@ -320,7 +320,7 @@ def test_bench_gpus2_launches_ranks():
     torch.distributed.run; here both share cuda:0 and exchange over gloo (ORBAMD_DIST_BACKEND /
     ORBAMD_BENCH_DEVICE, the one-GPU rehearsal hooks): n_gpus 2, both agents' slots checked, bit-exact."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
-           "--batch", "256", "--pipes", "2", "--no-cpu", "--sustain", "0", "--ingest-steps", "0"]
+           "--batch", "256", "--pipes", "2", "--full", "--no-cpu", "--sustain", "0", "--ingest-steps", "0"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(ORBAMD_DIST_BACKEND="gloo", ORBAMD_BENCH_DEVICE="0")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=400, cwd=ROOT, env=env)

@@ -13,11 +13,11 @@ done
 summ='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d["stage_ms_per_step"]; print("%.0f" % d["value"], " ".join("%s=%.3f" % (k, s[k]) for k in ("pyramid","fast_cells","octree","blur","describe","match")))'
 for r in $(seq 1 ${AB_ROUNDS:-3}); do
   for v in "$@"; do
-    out=$(ORBAMD_LIB_VARIANT=$v timeout -k 10 120 python bench.py --sustain 0 --no-cpu --steps 30 ${AB_ARGS} | python -c "$summ") || exit $?
+    out=$(ORBAMD_LIB_VARIANT=$v timeout -k 10 120 python bench.py --full --sustain 0 --no-cpu --steps 30 ${AB_ARGS} | python -c "$summ") || exit $?
     echo "r$r $v overlapped: $out"
   done
 done
 for v in "$@"; do
-  out=$(ORBAMD_LIB_VARIANT=$v timeout -k 10 120 python bench.py --sustain 0 --no-cpu --steps 30 ${AB_ARGS} --pipes 1 --batch 256 --serial-stages | python -c "$summ") || exit $?
+  out=$(ORBAMD_LIB_VARIANT=$v timeout -k 10 120 python bench.py --full --sustain 0 --no-cpu --steps 30 ${AB_ARGS} --pipes 1 --batch 256 --serial-stages | python -c "$summ") || exit $?
   echo "$v serial-1graph: $out"
 done

@@ -6,7 +6,7 @@
 T=$1; R=${2:-3}
 mkdir -p gpurun_out
 summ='import sys,json; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith("{")][-1]); print("%.0f bit_exact=%s exch=%.3f ag=%.4f %s" % (d["value"], d["bit_exact"], d["stage_ms_per_step"].get("exchange",0), d["stage_ms_per_step"].get("allgather",0), d["collective"][:60]))'
-common="--steps 200 --warmup 20 --no-cpu --sustain 0 --ingest-steps 0"
+common="--full --steps 200 --warmup 20 --no-cpu --sustain 0 --ingest-steps 0"
 port=29611
 for r in $(seq 1 $R); do
   out=$(timeout -k 10 150 python3 bench.py $common | python3 -c "$summ") || exit $?

@@ -13,7 +13,7 @@ done
 summ='import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); s=d["stage_ms_per_step"]; print("%.0f" % d["value"], "bit_exact=%s" % d["bit_exact"], " ".join("%s=%.3f" % (k, s[k]) for k in ("pyramid","fast_cells","octree","blur","describe","match")))'
 for r in 1 2 3; do
   for v in "$@"; do
-    out=$(env $v timeout -k 10 120 python bench.py --sustain 0 --no-cpu --ingest-steps 0 ${AB_ARGS} | python -c "$summ") || exit $?
+    out=$(env $v timeout -k 10 120 python bench.py --full --sustain 0 --no-cpu --ingest-steps 0 ${AB_ARGS} | python -c "$summ") || exit $?
     echo "r$r $v: $out"
   done
 done

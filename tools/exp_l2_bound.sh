@@ -6,7 +6,7 @@
 export TMPDIR=/tmp
 mkdir -p gpurun_out
 summ='import sys,json; d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith("{")][-1]); s=d["stage_ms_per_step"]; print("%.0f frames/s" % d["value"], " ".join("%s=%.3f" % (k, s[k]) for k in ("pyramid","fast_cells","octree","blur","describe","match")))'
-B="python3 bench.py --no-cpu --sustain 0 --ingest-steps 0 --steps 100 --warmup 10"
+B="python3 bench.py --full --no-cpu --sustain 0 --ingest-steps 0 --steps 100 --warmup 10"
 for r in 1 2 3; do
   for m in "" "--alias-frames"; do
     out=$(timeout -k 10 120 $B $m | python3 -c "$summ") || exit $?

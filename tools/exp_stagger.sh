@@ -8,7 +8,7 @@ for r in $(seq 1 "$R"); do
   for m in each once none; do
     for st in "20 5" "200 20"; do
       set -- $st
-      v=$(timeout -k 10 120 python bench.py --sustain 0 --no-cpu --ingest-steps 0 --steps $1 --warmup $2 --stagger $m \
+      v=$(timeout -k 10 120 python bench.py --full --sustain 0 --no-cpu --ingest-steps 0 --steps $1 --warmup $2 --stagger $m \
           | python -c "$summ") || exit $?
       echo "r$r stagger=$m steps=$1 warmup=$2: $v"
     done

@@ -36,10 +36,10 @@ for step in "$@"; do
       tools/prof_reduce.sh $T $sub
       cp gpurun_out/${T}_pmc_traffic.json profiles/pmc_traffic.json ;;  # the bench steps that follow read it
     prof_cfg) for c in c3 c4; do tools/pmc_config.sh $c || exit $?; done ;;
-    bench_driver) tools/gpu_run.sh "300 ${T}_bench_driver python3 bench.py --gpus 1 --steps 20 --warmup 5" || exit $? ;;
-    bench) tools/gpu_run.sh "300 ${T}_bench python3 bench.py" || exit $? ;;
-    c3) tools/gpu_run.sh "300 ${T}_bench_c3 python3 bench.py --config c3 --gpus 1 --steps 20 --warmup 5" || exit $? ;;
-    c4) tools/gpu_run.sh "300 ${T}_bench_c4 python3 bench.py --config c4 --gpus 1 --steps 20 --warmup 5" || exit $? ;;
+    bench_driver) tools/gpu_run.sh "300 ${T}_bench_driver python3 bench.py --full --gpus 1 --steps 20 --warmup 5" || exit $? ;;
+    bench) tools/gpu_run.sh "300 ${T}_bench python3 bench.py --full" || exit $? ;;
+    c3) tools/gpu_run.sh "300 ${T}_bench_c3 python3 bench.py --full --config c3 --gpus 1 --steps 20 --warmup 5" || exit $? ;;
+    c4) tools/gpu_run.sh "300 ${T}_bench_c4 python3 bench.py --full --config c4 --gpus 1 --steps 20 --warmup 5" || exit $? ;;
     latency) tools/gpu_run.sh "300 ${T}_latency tests/cpp/build/bench_latency 2000" || exit $? ;;
     dropin) tools/gpu_run.sh "300 ${T}_dropin_latency tests/cpp/build/bench_dropin_latency 2000" || exit $? ;;
     *) echo "unknown step $step"; exit 2 ;;

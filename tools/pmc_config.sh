@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 C=$1
 R=$GRAFT_REPO_ROOT
-B="python3 bench.py --config $C --steps 2 --warmup 1 --no-cpu --sustain 0"
+B="python3 bench.py --full --config $C --steps 2 --warmup 1 --no-cpu --sustain 0"
 tools/gpu_run.sh \
   "300 pmc_${C}_a rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU --output-format csv -d $R/gpurun_out/pmc_${C}_a -o run -- $B" \
   "300 pmc_${C}_fetch rocprofv3 --pmc FETCH_SIZE --output-format csv -d $R/gpurun_out/pmc_${C}_fetch -o run -- $B" \

@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 T=${1:-r01}
 R=$GRAFT_REPO_ROOT
-tools/gpu_run.sh "300 ${T}_bench python3 bench.py" || exit $?
+tools/gpu_run.sh "300 ${T}_bench python3 bench.py --full" || exit $?
 cp gpurun_out/${T}_bench.log gpurun_out/${T}_bench.json
 tools/prof_round.sh "$T" || exit $?
 tools/gpu_run.sh \

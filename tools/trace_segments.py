@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
 """Average duration of each pipeline kernel per segment of a `bench.py` run, from a rocprofv3 kernel trace.
 
-bench.py launches every stage kernel once per graph and step in this order: warm-up steps, the untimed
+bench.py --full launches every stage kernel once per graph and step in this order: warm-up steps, the untimed
 stage-split pass, the timed region, the `roofline.alone` launches (graph 0's extraction alone on the GPU, ALONE
 launches of every extraction stage: 7 per priced kernel), the extract-only pass, (match-only: no extraction kernels),
 then the ingest leg. rocprofv3 --stats averages over all of them; the ingest leg's launches overlap differently
 (PCIe-bound steps), so the timed region's own average is what bench.py's event-timed `launch_ms` is
-compared with.
+compared with. A trace of a plain run (no --full: (WARMUP + STEPS) x PIPES launches of a kernel) holds the warm-up
+steps and the timed region only, and is split so.
 usage: trace_segments.py run_kernel_trace.csv STEPS WARMUP [PIPES] [ALONE]"""
 import csv
 import sys
@@ -33,7 +34,9 @@ def main():
             continue
         d = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e6 for r in ks]
         segs = [("warmup", 0, w), ("stage_split", w, w + s), ("timed", w + s, w + 2 * s)]
-        if stage in ("match", "stereo"):  # not in the alone launches; the matcher runs in the match-only pass
+        if len(d) == w + s:  # a plain run
+            segs = [("warmup", 0, w), ("timed", w, w + s)]
+        elif stage in ("match", "stereo"):  # not in the alone launches; the matcher runs in the match-only pass
             segs += [("match_only" if stage == "match" else "extract_only", w + 2 * s, w + 3 * s),
                      ("ingest", w + 3 * s, len(d))]
         else:
