@@ -279,10 +279,16 @@ __global__ __launch_bounds__(kStereoThreads) void k_stereo(StereoArgs a, const i
         const float iniu = __fsub_rn(__fadd_rn(suR0, 5.0f), 5.0f);
         const float endu = __fadd_rn(__fadd_rn(__fadd_rn(suR0, 5.0f), 5.0f), 1.0f);
         const int lw = a.lw[levelL], lh = a.lh[levelL];
-        corr = corr && !(iniu < 0 || endu >= (float)lw);
         const int r0 = (int)__fsub_rn(svL, 5.0f), c0l = (int)__fsub_rn(suL, 5.0f), c0r = (int)__fsub_rn(suR0, 10.0f);
-        if (corr && (r0 < 0 || r0 + 11 > lh || c0l < 0 || c0l + 11 > lw || c0r < 0 || c0r + 21 > lw)) {
-            if (li == 0) atomicOr(err, 2);  // the reference's cv::Mat::colRange/rowRange would assert
+        // the reference takes the left window (Frame.cc:574: cv::Mat::colRange/rowRange would assert) before it
+        // tests iniu / endu (Frame.cc:586), and the right windows after: the error is raised in that order
+        if (corr && (r0 < 0 || r0 + 11 > lh || c0l < 0 || c0l + 11 > lw)) {
+            if (li == 0) atomicOr(err, 2);
+            corr = false;
+        }
+        corr = corr && !(iniu < 0 || endu >= (float)lw);
+        if (corr && (c0r < 0 || c0r + 21 > lw)) {
+            if (li == 0) atomicOr(err, 2);
             corr = false;
         }
         int pitchL = 0, pitchR = 0;

@@ -19,11 +19,21 @@ def roundf(v):
     return f32(fl + (1 if v - fl >= 0.5 else 0))
 
 
-def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb):
-    """Pure-Python restatement of Frame::ComputeStereoMatches (Frame.cc:470-641)."""
+def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb, stats=None):
+    """Pure-Python restatement of Frame::ComputeStereoMatches (Frame.cc:470-641). `stats` (a dict) receives the
+    exit each left keypoint took ("exit": list of names, "count": exit -> number) and what the scene exercised:
+    hamming_tie, sad_tie, deltaR_nz, branch_001, matched_level / kept_level (per pyramid level), max_sad (the
+    largest L1 distance evaluated at any shift), median, th_dist."""
     tabs = ol.tables()
     scale, inv = tabs["scale"], tabs["inv_scale"]
     N = len(kl)
+    st = {"exit": ["?"] * N, "count": {}, "hamming_tie": 0, "sad_tie": 0, "deltaR_nz": 0, "branch_001": 0,
+          "matched_level": [0] * 8, "kept_level": [0] * 8, "max_sad": 0, "median": None, "th_dist": None}
+
+    def leave(i, name):
+        st["exit"][i] = name
+        st["count"][name] = st["count"].get(name, 0) + 1
+
     ur = np.full(N, -1, np.float32)
     dp = np.full(N, -1, np.float32)
     nRows = ol.level_size(0)[1]
@@ -34,7 +44,8 @@ def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb):
         maxr = int(np.ceil(f32(y + r)))
         minr = int(np.floor(f32(y - r)))
         for yi in range(minr, maxr + 1):
-            rows[yi].append(iR)
+            if 0 <= yi < nRows:  # outside is undefined behaviour in the reference
+                rows[yi].append(iR)
     maxD = f32(mbf) / f32(mb)
     pyrL = [ol.pyramid(l) for l in range(8)]
     pyrR = [orr.pyramid(l) for l in range(8)]
@@ -46,9 +57,10 @@ def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb):
         vL, uL = f32(kl["y"][iL]), f32(kl["x"][iL])
         cand = rows[int(vL)]
         if not cand:
+            leave(iL, "no_cand")
             continue
         minU, maxU = f32(uL - maxD), uL
-        best, bestR = 100, 0
+        best, bestR, nbest = 100, 0, 0
         for iR in cand:
             o = int(kr["octave"][iR])
             if o < lev - 1 or o > lev + 1:
@@ -57,31 +69,42 @@ def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb):
             if minU <= uR <= maxU:
                 d = int(np.count_nonzero(hd[iL] != hr[iR]))
                 if d < best:
-                    best, bestR = d, iR
+                    best, bestR, nbest = d, iR, 1
+                elif d == best:
+                    nbest += 1
         if best >= 75:
+            leave(iL, "hamming")
             continue
+        st["hamming_tie"] += nbest > 1
         sf = inv[lev]
         suL = roundf(f32(uL * sf))
         svL = roundf(f32(vL * sf))
         suR0 = roundf(f32(f32(kr["x"][bestR]) * sf))
         PL, PR = pyrL[lev], pyrR[lev]
         r0, c0 = int(svL) - 5, int(suL) - 5
+        assert r0 >= 0 and c0 >= 0 and r0 + 11 <= PL.shape[0] and c0 + 11 <= PL.shape[1], "the reference throws"
         IL = PL[r0:r0 + 11, c0:c0 + 11].astype(np.int64)
         IL = IL - IL[5, 5]
         if suR0 < 0 or suR0 + 11 >= PR.shape[1]:
+            leave(iL, "right_edge")
             continue
+        assert suR0 >= 10, "the reference throws"
         vd = []
         for inc in range(-5, 6):
             cc = int(suR0) + inc - 5
             IR = PR[r0:r0 + 11, cc:cc + 11].astype(np.int64)
             IR = IR - IR[5, 5]
             vd.append(int(np.abs(IL - IR).sum()))
+        st["max_sad"] = max(st["max_sad"], max(vd))
         bi = int(np.argmin(vd))  # first minimum, like `dist < bestDist`
         if bi in (0, 10):
+            leave(iL, "end_shift")
             continue
+        st["sad_tie"] += vd.count(vd[bi]) > 1
         d1, d2, d3 = f32(vd[bi - 1]), f32(vd[bi]), f32(vd[bi + 1])
         deltaR = f32(f32(d1 - d3) / f32(f32(2) * f32(f32(d1 + d3) - f32(2) * d2)))
         if deltaR < -1 or deltaR > 1:
+            leave(iL, "deltaR_range")
             continue
         bestuR = f32(scale[lev] * f32(f32(suR0 + f32(bi - 5)) + deltaR))
         disp = f32(uL - bestuR)
@@ -89,19 +112,33 @@ def stereo_py(ol, orr, kl, dl, kr, dr, mbf, mb):
             if disp <= 0:
                 disp = f32(0.01)
                 bestuR = f32(float(uL) - 0.01)
+                st["branch_001"] += 1
             dp[iL] = f32(f32(mbf) / disp)
             ur[iL] = bestuR
             vdi.append((vd[bi], iL))
+            st["deltaR_nz"] += deltaR != 0
+            st["matched_level"][lev] += 1
+            leave(iL, "kept")
+        else:
+            leave(iL, "neg_disp" if disp < 0 else "maxD")
     vdi.sort()
     kept = len(vdi)
     if vdi:
         med = f32(vdi[len(vdi) // 2][0])
         th = f32(f32(f32(1.5) * f32(1.4)) * med)
+        st["median"], st["th_dist"] = float(med), float(th)
         for d, i in reversed(vdi):
             if f32(d) < th:
                 break
             ur[i] = dp[i] = -1
             kept -= 1
+            st["count"]["kept"] -= 1
+            leave(i, "median_rej")
+    for i in range(N):
+        if st["exit"][i] == "kept":
+            st["kept_level"][int(kl["octave"][i])] += 1
+    if stats is not None:
+        stats.update(st)
     return ur, dp, kept
 
 
@@ -134,6 +171,126 @@ def test_stereo_oracle_no_right_keypoints():
     orr(np.full((H, W), 128, np.uint8))  # flat right image: no keypoints
     ur, dp, n = oracle_py.compute_stereo_matches(ol, orr, kl, dl, kl[:0], dl[:0], 40.0, 0.1)
     assert n == 0 and (ur == -1).all() and (dp == -1).all()
+
+
+# ---- varied disparities and hand-made edge cases (stereo_scenes.py). The coverage conditions are asserted here, from
+# the restatement's stats, never from the code under test; the GPU tests run the same scenes (test_gpu_stereo.py).
+import stereo_scenes as ss  # noqa: E402
+
+MBF, MB = 47.90639384423901, 0.11
+
+
+def _same_bits(res, ref):
+    assert res[2] == ref[2]
+    np.testing.assert_array_equal(res[0].view(np.uint32), ref[0].view(np.uint32))
+    np.testing.assert_array_equal(res[1].view(np.uint32), ref[1].view(np.uint32))
+
+
+@pytest.mark.parametrize("W,seed,bands", ss.BAND_CASES)
+def test_stereo_band_scene_oracle_matches_restatement(W, seed, bands):
+    L, R = ss.band_scene(seed, W, 240, bands)
+    ol = oracle_py.OracleExtractor(500, 1.2, 8, 20, 7)
+    orr = oracle_py.OracleExtractor(500, 1.2, 8, 20, 7)
+    kl, dl = ol(L)
+    kr, dr = orr(R)
+    st = {}
+    res = stereo_py(ol, orr, kl, dl, kr, dr, MBF, MB, st)
+    _same_bits(oracle_py.compute_stereo_matches(ol, orr, kl, dl, kr, dr, MBF, MB), res)
+    c = st["count"]
+    matched = c["kept"] + c["median_rej"]
+    assert c["median_rej"] > 0 and c["end_shift"] > 0 and c["neg_disp"] > 0
+    assert st["deltaR_nz"] > 0.9 * matched
+    assert min(st["kept_level"]) >= 1
+    assert res[2] == c["kept"] >= 0.1 * len(kl)
+    assert c.get("deltaR_range", 0) == 0  # |deltaR| <= 0.5 always (module docstring of test_gpu_stereo.py)
+
+
+def test_stereo_band_scene_left_image_is_shared():
+    """BANDS and BANDS_ALT give two right images for one left image (the batch test pairs it with both)"""
+    for W, seed in ss.BAND_SHARED_SEED.items():
+        assert (W, seed, ss.BANDS) in ss.BAND_CASES and (W, seed, ss.BANDS_ALT) in ss.BAND_CASES
+        a, b = ss.band_scene(seed, W, 240, ss.BANDS), ss.band_scene(seed, W, 240, ss.BANDS_ALT)
+        assert (a[0] == b[0]).all() and (a[1] != b[1]).any()
+
+
+@pytest.fixture(scope="module", params=[320, 323, 376, 375])
+def directed(request):
+    c = ss.directed_cases(request.param, 240)
+    ol = oracle_py.OracleExtractor(500, 1.2, 8, 20, 7)
+    orr = oracle_py.OracleExtractor(500, 1.2, 8, 20, 7)
+    ol(c["left"])
+    orr(c["right"])
+    return c, ol, orr
+
+
+def test_stereo_directed_tables(directed):
+    c, ol, _ = directed
+    scale, inv, sizes = ss.tables(c["left"].shape[1], 240)
+    np.testing.assert_array_equal(ol.tables()["scale"], scale)
+    np.testing.assert_array_equal(ol.tables()["inv_scale"], inv)
+    assert [ol.level_size(l) for l in range(8)] == sizes
+    assert any(w % 4 for w, _ in sizes[1:])  # a level above 0 whose width is no multiple of 4
+    kl, kr = c["kl"], c["kr"]
+    for k in (kl, kr):  # every input valid
+        assert (k["octave"] >= 0).all() and (k["octave"] < 8).all()
+        assert (k["x"] >= 0).all() and (k["x"] <= c["left"].shape[1] - 1).all()
+        assert (k["y"] >= 0).all() and (k["y"] <= 239).all()
+    assert len(kr) > len(kl) and len(kl) % 16 != 0
+
+
+def test_stereo_directed_oracle_matches_restatement(directed):
+    c, ol, orr = directed
+    st = {}
+    res = stereo_py(ol, orr, c["kl"], c["dl"], c["kr"], c["dr"], c["mbf"], c["mb"], st)
+    _same_bits(oracle_py.compute_stereo_matches(ol, orr, c["kl"], c["dl"], c["kr"], c["dr"], c["mbf"], c["mb"]), res)
+    for i, name in enumerate(c["names"]):
+        assert st["exit"][i] in c["expect"][name], "%s ended in %s" % (name, st["exit"][i])
+    assert st["max_sad"] == 61200  # 120 * 510, 33 150 of it in one 16-bit half
+    assert st["branch_001"] == 1 and st["hamming_tie"] == 2 and st["sad_tie"] == 1
+    assert st["count"].get("deltaR_range", 0) == 0
+    # 1.5f * 1.4f * 10 lies half-way between 21 and the float below it and rounds to 21: sad_21 is not < it, sad_20 is
+    assert st["median"] == 10 and 20 < st["th_dist"] <= 21
+    assert res[2] == st["count"]["kept"] > 0
+    ur, dp = res[0], res[1]
+    i = c["names"].index("branch001")
+    assert ur[i] == f32(float(c["kl"]["x"][i]) - 0.01) and dp[i] == f32(f32(c["mbf"]) / f32(0.01))
+    x = {n: float(c["kl"]["x"][j]) - float(ur[j]) for j, n in enumerate(c["names"])}  # disparities
+    assert abs(x["hamming_tie"] - 4) < 0.5 and abs(x["many_cands"] - 4) < 0.5  # the lower iR of the tie, not the 28 px copy
+    assert abs(x["sad_tie_first"] - 6) < 0.5  # shift 3 of the tied 3, 5, 7, 9
+    assert abs(x["uR_eq_minU"] - 39) < 0.5 and abs(x["uR_eq_maxU"] - 2) < 0.5
+    assert abs(x["shift_1"] - 6) < 0.5 and abs(x["shift_9"] - 6) < 0.5 and abs(x["border_right"] - 6) < 0.5
+    # the second trip of 64 candidates: many_cands has more than 64 right keypoints in the buckets of its band
+    j = c["names"].index("many_cands")
+    r = f32(2.0) * ol.tables()["scale"][c["kr"]["octave"]]
+    minr = np.floor(c["kr"]["y"] - r)
+    v = int(c["kl"]["y"][j])
+    assert np.count_nonzero((minr <= v) & (minr >= v - 4)) > 64
+
+
+@pytest.mark.parametrize("name", sorted(ss.MEDIAN_SUBSETS))
+def test_stereo_directed_median_subsets(directed, name):
+    c, ol, orr = directed
+    names, median, kept = ss.MEDIAN_SUBSETS[name]
+    kl, dl = ss.subset(c, names)
+    st = {}
+    res = stereo_py(ol, orr, kl, dl, c["kr"], c["dr"], c["mbf"], c["mb"], st)
+    _same_bits(oracle_py.compute_stereo_matches(ol, orr, kl, dl, c["kr"], c["dr"], c["mbf"], c["mb"]), res)
+    assert st["median"] == median and res[2] == kept
+    assert len(kl) < 16 or len(kl) % 16
+
+
+def test_stereo_oracle_raises_on_throw_cases(directed):
+    c, ol, orr = directed
+    cases = ss.throw_cases(c["left"].shape[1], 240)
+    assert [t[0] for t in cases] == ["left_window_only", "both"]
+    for name, kl, dl, kr, dr in cases:
+        with pytest.raises(RuntimeError):
+            oracle_py.compute_stereo_matches(ol, orr, kl, dl, kr, dr, c["mbf"], c["mb"])
+        # without the offending keypoint the call is fine
+        oracle_py.compute_stereo_matches(ol, orr, kl[:-1], dl[:-1], kr, dr, c["mbf"], c["mb"])
+    # `both`: the best right keypoint fails Frame.cc:586's iniu / endu test as well
+    kr = cases[1][3]
+    assert kr["x"][-1] + 11 >= c["left"].shape[1] and cases[0][3]["x"][-1] + 11 < c["left"].shape[1]
 
 
 # ------------------------------------------------------------------ SearchByProjection
