@@ -74,6 +74,57 @@ def test_projection_edge_cases():
     _same(mt.SearchByProjectionLocal(F, same, 4.0), oracle_py.search_by_projection_local(F, same, 4.0, 0.8))
 
 
+# ---- hand-made cases (proj_cases.py; what each case reaches is asserted on the CPU, in test_oracle_frame.py). One
+# matcher, hence one device context with its scratch, scan / result buffers and pinned result words, serves every
+# call of every group, the 40 000-feature frame first: something stale from a larger call would show in a smaller one.
+import proj_cases as pc  # noqa: E402
+
+
+@pytest.fixture(scope="module")
+def shared_matcher():
+    mt = orbamd.ORBmatcher(0.8, False)
+    yield mt
+    mt.close()
+
+
+def _same_case(g, c, res, ref):
+    (ng, mg), (no, mo) = res, ref
+    assert mg.shape == mo.shape
+    bad = np.nonzero(mg != mo)[0]
+    if c["kind"].startswith("fuse"):  # best_idx per MapPoint
+        where = g.describe(c, queries=bad, feats=[v for v in list(mg[bad]) + list(mo[bad]) if v >= 0])
+    else:  # match per feature
+        where = g.describe(c, feats=bad, queries=[v for v in list(mg[bad]) + list(mo[bad]) if v >= 0])
+    assert bad.size == 0, "gpu %s oracle %s at %s" % (mg[bad[:8]], mo[bad[:8]], where)
+    assert ng == no, "%s/%s: count %d, oracle %d" % (g.name, c["key"], ng, no)
+
+
+@pytest.mark.parametrize("gname", pc.GROUPS)
+def test_projection_cases(gname, shared_matcher):
+    """every call of the group (SearchByProjection x4 with its flags, Fuse, FuseSim3): the whole match / best_idx
+    array and the count equal the oracle's"""
+    g = pc.group(gname)
+    for c, F, mps in g.calls():
+        _same_case(g, c, pc.run_gpu(shared_matcher, c, F, mps), pc.run_oracle(c, F, mps))
+
+
+@pytest.mark.parametrize("gname", pc.FUSE_GROUPS)
+def test_projection_cases_fuse_cached(gname, shared_matcher):
+    """the Fuse calls with the frame and its grid held in a KeyFrameCache: the first call builds the entry (k_grid),
+    the second finds it"""
+    g = pc.group(gname)
+    calls = [t for t in g.calls() if t[0]["kind"] == "fuse"]
+    assert calls and all(F.n > 0 for _, F, _ in calls)
+    cache = orbamd.KeyFrameCache()
+    for c, F, mps in calls:
+        ref = pc.run_oracle(c, F, mps)
+        for _ in range(2):
+            _same_case(g, c, pc.run_gpu(shared_matcher, c, F, mps, cache, 1 + pc.GROUPS.index(gname)), ref)
+    st = cache.stats()
+    assert st["misses"] == 1 and st["hits"] == 2 * len(calls) - 1
+    cache.close()
+
+
 def test_distinctive_descriptors_batch():
     from test_oracle_frame import distinctive_scene
     off, desc = distinctive_scene(2, big=True)

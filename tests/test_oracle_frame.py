@@ -298,6 +298,15 @@ import proj_scenes as ps  # noqa: E402
 
 
 def grid_py(F):
+    """Frame::AssignFeaturesToGrid + PosInGrid (Frame.cc:235-250, 391-401); kept on the view together with the bytes
+    it was made from (a 40 000-feature frame is gridded once, not once per call; a changed x or y makes a new grid)"""
+    key = (F.n, F.x.tobytes(), F.y.tobytes(), float(F.min_x), float(F.min_y), float(F.grid_w_inv), float(F.grid_h_inv))
+    if getattr(F, "_grid_py", (None, None))[0] != key:
+        F._grid_py = (key, _grid_py(F))
+    return F._grid_py[1]
+
+
+def _grid_py(F):
     g = {}
     for i in range(F.n):
         px = int(roundf_signed(f32(f32(F.x[i] - F.min_x) * F.grid_w_inv)))
@@ -341,15 +350,56 @@ def area_py(F, g, x, y, r, minL=-1, maxL=-1):
     return out
 
 
-def local_py(F, mp, th, nnratio):
+class _Stats:
+    """What a restatement did with each MapPoint i: exit[i] (skipped, depth, out_of_image, dist_range, view_angle,
+    no_candidates, th_reject, ratio_reject, accepted, and after the loop overwritten / rot_removed), uv[i] / radius[i]
+    / level[i] of the search, ncand[i] = len(vIndices), ranked[i] = [(dist, scan position, idx)] of the candidates that
+    pass every per-candidate test but the occupancy one, sorted (what a scan that ignores claims would list),
+    occ_seen[i] = the idx of ranked[i] that were occupied at that moment, best[i] / second[i] = (dist, idx) kept by
+    the loop, rot[i] = (bin, rot * factor) of an accepted query, hist / kept_bins of the rotation filter."""
+
+    def __init__(self, n):
+        self.d = {k: [None] * n for k in ("uv", "radius", "level", "ranked", "occ_seen", "best", "second", "rot")}
+        self.d["exit"] = ["?"] * n
+        self.d["ncand"] = [0] * n
+        self.d["hist"] = None
+        self.d["kept_bins"] = None
+
+    def leave(self, i, name):
+        self.d["exit"][i] = name
+
+    def search(self, i, u, v, radius, level, ncand):
+        self.d["uv"][i], self.d["radius"][i], self.d["level"][i] = (f32(u), f32(v)), f32(radius), level
+        self.d["ncand"][i] = ncand
+
+    def cands(self, i, lst, occ):
+        """lst: (dist, scan position, idx) in scan order"""
+        self.d["ranked"][i] = sorted(lst)
+        self.d["occ_seen"][i] = [k for _, _, k in lst if occ[k]]
+
+    def finish(self, match, stats):
+        keep = self.d["kept_bins"]
+        for i, e in enumerate(self.d["exit"]):
+            if e == "accepted" and keep is not None and self.d["rot"][i][0] not in keep:
+                self.d["exit"][i] = "rot_removed"
+            elif e == "accepted" and match[self.d["best"][i][1]] != i:
+                self.d["exit"][i] = "overwritten"  # by a later query, or reset through another query's bin
+        self.d["any_occ"] = [bool(o) for o in self.d["occ_seen"]]
+        if stats is not None:
+            stats.update(self.d)
+
+
+def local_py(F, mp, th, nnratio, stats=None):
     """ORBmatcher::SearchByProjection(Frame&, vector<MapPoint*>, th) (ORBmatcher.cc:45-129)."""
     g = grid_py(F)
     bits = np.unpackbits(F.desc, axis=1)
-    occ = F.occupied.astype(bool).copy()
+    occ = F.occupied.astype(bool).copy() if F.occupied is not None else np.zeros(F.n, bool)
     match = np.full(F.n, -1, np.int32)
+    st = _Stats(mp.n)
     nm = 0
     for i in range(mp.n):
-        if not mp.track_in_view[i] or mp.bad[i]:
+        if not mp.track_in_view[i] or (mp.bad is not None and mp.bad[i]):
+            st.leave(i, "skipped")
             continue
         lvl = int(mp.track_level[i])
         r = f32(2.5) if float(mp.track_view_cos[i]) > 0.998 else f32(4.0)
@@ -357,24 +407,310 @@ def local_py(F, mp, th, nnratio):
             r = f32(r * f32(th))
         rad = f32(r * F.scale_factors[lvl])
         qb = np.unpackbits(mp.desc[i])
-        best, bl, best2, bl2, bi = 256, -1, 256, -1, -1
-        for idx in area_py(F, g, mp.track_proj_x[i], mp.track_proj_y[i], rad, lvl - 1, lvl):
-            if occ[idx]:
-                continue
+        best, bl, best2, bl2, bi, si = 256, -1, 256, -1, -1, -1
+        cand = area_py(F, g, mp.track_proj_x[i], mp.track_proj_y[i], rad, lvl - 1, lvl)
+        st.search(i, mp.track_proj_x[i], mp.track_proj_y[i], rad, lvl, len(cand))
+        if not cand:
+            st.leave(i, "no_candidates")
+            continue
+        seen = []
+        for pos, idx in enumerate(cand):
             if F.uright is not None and F.uright[idx] > 0:
                 if abs(f32(mp.track_proj_xr[i] - F.uright[idx])) > rad:
                     continue
             dist = int(np.count_nonzero(bits[idx] != qb))
+            if dist < 256:
+                seen.append((dist, pos, idx))
+            if occ[idx]:  # (the reference tests this first; neither test has a side effect)
+                continue
             if dist < best:
-                best2, best, bl2, bl, bi = best, dist, bl, int(F.octave[idx]), idx
+                best2, best, bl2, bl, si, bi = best, dist, bl, int(F.octave[idx]), bi, idx
             elif dist < best2:
-                bl2, best2 = int(F.octave[idx]), dist
+                bl2, best2, si = int(F.octave[idx]), dist, idx
+        st.cands(i, seen, occ)
+        st.d["best"][i], st.d["second"][i] = (best, bi), (best2, si)
         if best <= 100:
             if bl == bl2 and f32(best) > f32(f32(nnratio) * f32(best2)):
+                st.leave(i, "ratio_reject")
                 continue
             match[bi] = i
-            occ[bi] = bool(mp.has_obs[i])
+            occ[bi] = bool(mp.has_obs[i]) if mp.has_obs is not None else False
             nm += 1
+            st.leave(i, "accepted")
+        else:
+            st.leave(i, "th_reject")
+    st.finish(match, stats)
+    return nm, match
+
+
+def _mat34(T):
+    T = np.asarray(T, np.float32).reshape(4, 4)
+    return [[f32(T[r][c]) for c in range(3)] for r in range(3)], [f32(T[r][3]) for r in range(3)]
+
+
+def _rt_neg(R, t):
+    """-R.t() * t: cv::gemm's generic path, double accumulation, one rounding (DESIGN.md)"""
+    return [f32(-1.0 * sum(float(R[k][i]) * float(t[k]) for k in range(3))) for i in range(3)]
+
+
+def _flag(a, i):
+    return a is not None and bool(a[i])
+
+
+def _three_maxima_py(sizes):
+    """ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1601-1642): the kept bins"""
+    ind, m = [-1, -1, -1], [0, 0, 0]
+    for i, s in enumerate(sizes):
+        if s > m[0]:
+            m, ind = [s, m[0], m[1]], [i, ind[0], ind[1]]
+        elif s > m[1]:
+            m, ind = [m[0], s, m[1]], [ind[0], i, ind[1]]
+        elif s > m[2]:
+            m[2], ind[2] = s, i
+    if f32(m[1]) < f32(f32(0.1) * f32(m[0])):
+        ind[1] = ind[2] = -1
+    elif f32(m[2]) < f32(f32(0.1) * f32(m[0])):
+        ind[2] = -1
+    return ind
+
+
+def _rot_push(hist, st, i, a1, a2, idx):
+    """ORBmatcher.cc:1431-1441 / 1560-1570"""
+    rot = f32(f32(a1) - f32(a2))
+    if rot < 0.0:
+        rot = f32(rot + f32(360.0))
+    p = f32(rot * f32(f32(1.0) / f32(30)))
+    b = int(roundf(p))
+    if b == 30:
+        b = 0
+    assert 0 <= b < 30
+    hist[b].append(idx)
+    st.d["rot"][i] = (b, p)
+
+
+def _rot_filter_py(hist, st, match, nm):
+    """ORBmatcher.cc:1447-1467 / 1577-1596 (-2 stands for the NULL the reference writes)"""
+    keep = _three_maxima_py([len(h) for h in hist])
+    st.d["hist"], st.d["kept_bins"] = [len(h) for h in hist], keep
+    for b in range(30):
+        if b not in keep:
+            for idx in hist[b]:
+                match[idx] = -2
+                nm -= 1
+    return nm
+
+
+def last_frame_py(F, Tcw, mp, Tl, th, bmono, check_ori, stats=None):
+    """ORBmatcher::SearchByProjection(Frame &CurrentFrame, const Frame &LastFrame, th, bMono) (ORBmatcher.cc:1328-1470)."""
+    hist = [[] for _ in range(30)]
+    Rcw, tcw = _mat34(Tcw)
+    twc = _rt_neg(Rcw, tcw)  # :1341
+    Rlw, tlw = _mat34(Tl)
+    tlc = _gemm33_fast(Rlw, twc, tlw)  # :1346
+    fwd = bool(tlc[2] > F.b) and not bmono
+    bwd = bool(f32(-tlc[2]) > F.b) and not bmono
+    g = grid_py(F)
+    bits = np.unpackbits(F.desc, axis=1)
+    occ = F.occupied.astype(bool).copy() if F.occupied is not None else np.zeros(F.n, bool)
+    match = np.full(F.n, -1, np.int32)
+    st = _Stats(mp.n)
+    st.d["forward"], st.d["backward"], st.d["tlc_z"] = fwd, bwd, tlc[2]
+    nm = 0
+    for i in range(mp.n):
+        if _flag(mp.skip, i):  # :1355-1357
+            st.leave(i, "skipped")
+            continue
+        x3 = _gemm33_fast(Rcw, [f32(c) for c in mp.pos[i]], tcw)
+        xc, yc = x3[0], x3[1]
+        invzc = f32(1.0 / float(x3[2]))
+        if invzc < 0:
+            st.leave(i, "depth")
+            continue
+        u = f32(f32(f32(F.fx * xc) * invzc) + F.cx)
+        v = f32(f32(f32(F.fy * yc) * invzc) + F.cy)
+        if u < F.min_x or u > F.max_x or v < F.min_y or v > F.max_y:
+            st.leave(i, "out_of_image")
+            continue
+        lo = int(mp.octave[i])
+        radius = f32(f32(th) * F.scale_factors[lo])
+        if fwd:
+            cand = area_py(F, g, u, v, radius, lo)
+        elif bwd:
+            cand = area_py(F, g, u, v, radius, 0, lo)
+        else:
+            cand = area_py(F, g, u, v, radius, lo - 1, lo + 1)
+        st.search(i, u, v, radius, lo, len(cand))
+        if not cand:
+            st.leave(i, "no_candidates")
+            continue
+        qb = np.unpackbits(mp.desc[i])
+        best, bi, seen = 256, -1, []
+        for pos, i2 in enumerate(cand):
+            if F.uright is not None and F.uright[i2] > 0:
+                ur = f32(u - f32(F.bf * invzc))
+                if abs(f32(ur - F.uright[i2])) > radius:
+                    continue
+            dist = int(np.count_nonzero(bits[i2] != qb))
+            if dist < 256:
+                seen.append((dist, pos, i2))
+            if occ[i2]:  # (tested first in the reference, :1403-1405)
+                continue
+            if dist < best:
+                best, bi = dist, i2
+        st.cands(i, seen, occ)
+        st.d["best"][i] = (best, bi)
+        if best <= 100:
+            match[bi] = i
+            occ[bi] = _flag(mp.has_obs, i)
+            nm += 1
+            st.leave(i, "accepted")
+            if check_ori:
+                _rot_push(hist, st, i, mp.angle[i], F.angle[bi], bi)
+        else:
+            st.leave(i, "th_reject")
+    if check_ori:
+        nm = _rot_filter_py(hist, st, match, nm)
+    st.finish(match, stats)
+    return nm, match
+
+
+def keyframe_py(F, Tcw, mp, th, orb_dist, check_ori, stats=None):
+    """ORBmatcher::SearchByProjection(Frame &CurrentFrame, KeyFrame *pKF, sAlreadyFound, th, ORBdist)
+    (ORBmatcher.cc:1472-1599)."""
+    Rcw, tcw = _mat34(Tcw)
+    Ow = _rt_neg(Rcw, tcw)
+    hist = [[] for _ in range(30)]
+    g = grid_py(F)
+    bits = np.unpackbits(F.desc, axis=1)
+    occ = F.occupied.astype(bool).copy() if F.occupied is not None else np.zeros(F.n, bool)
+    match = np.full(F.n, -1, np.int32)
+    st = _Stats(mp.n)
+    nm = 0
+    for i in range(mp.n):
+        if _flag(mp.skip, i) or _flag(mp.bad, i):  # :1492-1494
+            st.leave(i, "skipped")
+            continue
+        p = [f32(c) for c in mp.pos[i]]
+        x3 = _gemm33_fast(Rcw, p, tcw)
+        xc, yc = x3[0], x3[1]
+        invzc = f32(1.0 / float(x3[2]))  # no sign test here (:1502)
+        u = f32(f32(f32(F.fx * xc) * invzc) + F.cx)
+        v = f32(f32(f32(F.fy * yc) * invzc) + F.cy)
+        if u < F.min_x or u > F.max_x or v < F.min_y or v > F.max_y:
+            st.leave(i, "out_of_image")
+            continue
+        PO = [f32(p[k] - Ow[k]) for k in range(3)]
+        d3 = _norm3(PO)
+        if d3 < f32(f32(0.8) * f32(mp.min_dist[i])) or d3 > f32(f32(1.2) * f32(mp.max_dist[i])):
+            st.leave(i, "dist_range")
+            continue
+        lvl = _predict_scale(mp.max_dist[i], d3, F)
+        radius = f32(f32(th) * F.scale_factors[lvl])
+        cand = area_py(F, g, u, v, radius, lvl - 1, lvl + 1)
+        st.search(i, u, v, radius, lvl, len(cand))
+        if not cand:
+            st.leave(i, "no_candidates")
+            continue
+        qb = np.unpackbits(mp.desc[i])
+        best, bi, seen = 256, -1, []
+        for pos, i2 in enumerate(cand):
+            dist = int(np.count_nonzero(bits[i2] != qb))
+            if dist < 256:
+                seen.append((dist, pos, i2))
+            if occ[i2]:
+                continue
+            if dist < best:
+                best, bi = dist, i2
+        st.cands(i, seen, occ)
+        st.d["best"][i] = (best, bi)
+        if best <= orb_dist:
+            match[bi] = i
+            occ[bi] = True
+            nm += 1
+            st.leave(i, "accepted")
+            if check_ori:
+                _rot_push(hist, st, i, mp.angle[i], F.angle[bi], bi)
+        else:
+            st.leave(i, "th_reject")
+    if check_ori:
+        nm = _rot_filter_py(hist, st, match, nm)
+    st.finish(match, stats)
+    return nm, match
+
+
+def _decompose_scw(Scw):
+    """ORBmatcher.cc:298-303 / 985-990: scw, Rcw = sRcw / scw, tcw = t / scw (convertTo with the float 1 / scw), Ow"""
+    Scw = np.asarray(Scw, np.float32).reshape(4, 4)
+    scw = f32(np.sqrt(sum(float(Scw[0][c]) * float(Scw[0][c]) for c in range(3))))
+    inv = f32(1.0 / float(scw))
+    R = [[f32(Scw[r][c] * inv) for c in range(3)] for r in range(3)]
+    t = [f32(Scw[r][3] * inv) for r in range(3)]
+    return R, t, _rt_neg(R, t)
+
+
+def sim3proj_py(KF, Scw, mp, th, stats=None):
+    """ORBmatcher::SearchByProjection(KeyFrame* pKF, cv::Mat Scw, vpPoints, vpMatched, int th) (ORBmatcher.cc:290-403)."""
+    Rcw, tcw, Ow = _decompose_scw(Scw)
+    g = grid_py(KF)
+    bits = np.unpackbits(KF.desc, axis=1)
+    occ = KF.occupied.astype(bool).copy() if KF.occupied is not None else np.zeros(KF.n, bool)  # vpMatched[idx]
+    match = np.full(KF.n, -1, np.int32)
+    st = _Stats(mp.n)
+    nm = 0
+    for i in range(mp.n):
+        if _flag(mp.bad, i) or _flag(mp.skip, i):  # :317
+            st.leave(i, "skipped")
+            continue
+        p = [f32(c) for c in mp.pos[i]]
+        pc = _gemm33_fast(Rcw, p, tcw)
+        if pc[2] < 0.0:
+            st.leave(i, "depth")
+            continue
+        invz = f32(f32(1) / pc[2])
+        x, y = f32(pc[0] * invz), f32(pc[1] * invz)
+        u = f32(f32(KF.fx * x) + KF.cx)
+        v = f32(f32(KF.fy * y) + KF.cy)
+        if not (u >= KF.min_x and u < KF.max_x and v >= KF.min_y and v < KF.max_y):  # KeyFrame::IsInImage
+            st.leave(i, "out_of_image")
+            continue
+        PO = [f32(p[k] - Ow[k]) for k in range(3)]
+        d3 = _norm3(PO)
+        if d3 < f32(f32(0.8) * f32(mp.min_dist[i])) or d3 > f32(f32(1.2) * f32(mp.max_dist[i])):
+            st.leave(i, "dist_range")
+            continue
+        if _dot3(PO, mp.normal[i]) < 0.5 * float(d3):
+            st.leave(i, "view_angle")
+            continue
+        lvl = _predict_scale(mp.max_dist[i], d3, KF)
+        radius = f32(f32(int(th)) * KF.scale_factors[lvl])
+        cand = area_py(KF, g, u, v, radius)
+        st.search(i, u, v, radius, lvl, len(cand))
+        if not cand:
+            st.leave(i, "no_candidates")
+            continue
+        qb = np.unpackbits(mp.desc[i])
+        best, bi, seen = 256, -1, []
+        for pos, idx in enumerate(cand):
+            kl = int(KF.octave[idx])
+            if kl < lvl - 1 or kl > lvl:
+                continue
+            dist = int(np.count_nonzero(bits[idx] != qb))
+            if dist < 256:
+                seen.append((dist, pos, idx))
+            if occ[idx]:  # (tested before the level in the reference, :375)
+                continue
+            if dist < best:
+                best, bi = dist, idx
+        st.cands(i, seen, occ)
+        st.d["best"][i] = (best, bi)
+        if best <= 50:
+            match[bi] = i
+            occ[bi] = True
+            nm += 1
+            st.leave(i, "accepted")
+        else:
+            st.leave(i, "th_reject")
+    st.finish(match, stats)
     return nm, match
 
 
@@ -387,17 +723,299 @@ def test_projection_local_oracle_matches_restatement(seed, stereo, th):
     np.testing.assert_array_equal(m, m2)
 
 
+@pytest.mark.parametrize("seed,bmono,forward,check_ori,th", [(4, False, 0, True, 7.0), (5, True, 0, True, 15.0),
+                                                             (6, False, 1, False, 7.0), (7, False, -1, True, 7.0)])
+def test_projection_last_frame_oracle_matches_restatement(seed, bmono, forward, check_ori, th):
+    F, Tcw, mps, Tl = ps.last_frame_scene(seed, bmono, not bmono, forward)
+    st = {}
+    n, m = oracle_py.search_by_projection_last_frame(F, Tcw, mps, Tl, th, bmono, check_ori)
+    n2, m2 = last_frame_py(F, Tcw, mps, Tl, th, bmono, check_ori, st)
+    assert n == n2 and n > F.n // 4
+    np.testing.assert_array_equal(m, m2)
+    # (the scene moves the last frame by 0.5 along z for forward = +-1: one of the two directions, never both)
+    assert (st["forward"] != st["backward"]) == (forward != 0 and not bmono) and not (st["forward"] and st["backward"])
+    assert not check_ori or "rot_removed" in st["exit"]
+
+
+@pytest.mark.parametrize("seed,th,orb_dist,check_ori", [(5, 10.0, 100, True), (9, 3.0, 64, False),
+                                                        (10, 10.0, 100, False)])
+def test_projection_keyframe_oracle_matches_restatement(seed, th, orb_dist, check_ori):
+    F, Tcw, mps = ps.keyframe_scene(seed)
+    n, m = oracle_py.search_by_projection_keyframe(F, Tcw, mps, th, orb_dist, check_ori)
+    n2, m2 = keyframe_py(F, Tcw, mps, th, orb_dist, check_ori)
+    assert n == n2 and n > F.n // 8
+    np.testing.assert_array_equal(m, m2)
+
+
+@pytest.mark.parametrize("seed,th", [(6, 10), (11, 3)])
+def test_projection_sim3_oracle_matches_restatement(seed, th):
+    F, Scw, mps = ps.sim3_scene(seed)
+    n, m = oracle_py.search_by_projection_sim3(F, Scw, mps, th)
+    n2, m2 = sim3proj_py(F, Scw, mps, th)
+    assert n == n2 and n > F.n // 8
+    np.testing.assert_array_equal(m, m2)
+
+
 def test_projection_variants_oracle_sanity():
+    """one scene per variant (the seeds this test always had): count and every element of the match array equal the
+    restatement's, where it used to look at the counts only"""
     F, Tcw, mps, Tl = ps.last_frame_scene(4)
     n, m = oracle_py.search_by_projection_last_frame(F, Tcw, mps, Tl, 7.0, False, True)
-    assert n > F.n // 4 and n >= (m >= 0).sum()  # has_obs == 0 claimers can be overwritten (last wins)
+    n2, m2 = last_frame_py(F, Tcw, mps, Tl, 7.0, False, True)
+    assert n == n2 and n > F.n // 4 and n >= (m >= 0).sum()  # has_obs == 0 claimers can be overwritten (last wins)
+    np.testing.assert_array_equal(m, m2)
     F, Tcw, mps = ps.keyframe_scene(5)
     n, m = oracle_py.search_by_projection_keyframe(F, Tcw, mps, 10.0, 100, True)
-    assert n > F.n // 4 and n == (m >= 0).sum()  # every claim occupies
+    n2, m2 = keyframe_py(F, Tcw, mps, 10.0, 100, True)
+    assert n == n2 and n > F.n // 4 and n == (m >= 0).sum()  # every claim occupies
+    np.testing.assert_array_equal(m, m2)
     F, Scw, mps = ps.sim3_scene(6)
     n, m = oracle_py.search_by_projection_sim3(F, Scw, mps, 10)
-    assert n > F.n // 8 and n == (m >= 0).sum()
+    n2, m2 = sim3proj_py(F, Scw, mps, 10)
+    assert n == n2 and n > F.n // 8 and n == (m >= 0).sum()
+    np.testing.assert_array_equal(m, m2)
 
+
+# ---- hand-made cases (proj_cases.py): oracle == restatement on every call of every group, and every named case
+# takes the exit it is built for (from the restatement's stats, so a case that stops reaching its edge fails here)
+import proj_cases as pc  # noqa: E402
+
+
+def run_py(c, F, mps, st):
+    k = c["kind"]
+    if k == "local":
+        return local_py(F, mps, c["th"], c["nnratio"], st)
+    if k == "last":
+        return last_frame_py(F, c["Tcw"], mps, c["Tl"], c["th"], c["bmono"], c["check_ori"], st)
+    if k == "keyframe":
+        return keyframe_py(F, c["Tcw"], mps, c["th"], c["orb_dist"], c["check_ori"], st)
+    if k == "sim3":
+        return sim3proj_py(F, c["Tcw"], mps, c["th"], st)
+    if k == "fuse":
+        R, t = _mat34(c["Tcw"])
+        return fuse_py(F, mps, c["th"], R, t, c["Ow"], c["inv"], stats=st)
+    R, t, Ow = _decompose_scw(c["Tcw"])
+    return fuse_py(F, mps, c["th"], R, t, Ow, sim3=True, stats=st)
+
+
+_py_results = {}
+
+
+def py_result(gname):
+    """[(call, F, mps, (count, array), stats)] of a group, computed once"""
+    if gname not in _py_results:
+        out = []
+        for c, F, mps in pc.group(gname).calls():
+            st = {}
+            out.append((c, F, mps, run_py(c, F, mps, st), st))
+        _py_results[gname] = out
+    return _py_results[gname]
+
+
+@pytest.mark.parametrize("gname", pc.GROUPS)
+def test_projection_cases_oracle_matches_restatement(gname):
+    g = pc.group(gname)
+    for c, F, mps, (n2, m2), st in py_result(gname):
+        n, m = pc.run_oracle(c, F, mps)
+        bad = np.nonzero(m != m2)[0]
+        fuse = c["kind"].startswith("fuse")
+        assert bad.size == 0, "oracle %s restatement %s at %s" % (m[bad[:8]], m2[bad[:8]], g.describe(
+            c, queries=bad if fuse else [v for v in list(m[bad]) + list(m2[bad]) if v >= 0], feats=() if fuse else bad))
+        assert n == n2, "%s/%s: count %d, restatement %d" % (gname, c["key"], n, n2)
+
+
+@pytest.mark.parametrize("gname", pc.GROUPS)
+def test_projection_cases_take_their_exits(gname):
+    g = pc.group(gname)
+    F = g.frame()
+    assert F.n < 65536 and all(0 <= o < 8 for o in F.octave) and np.isfinite(F.x).all() and np.isfinite(F.y).all()
+    wrong = []
+    for c, F, mps, (n, m), st in py_result(gname):
+        names = g.names(c)
+        assert len(names) == mps.n and "?" not in st["exit"]
+        for i, name in enumerate(names):
+            e = g.expected(c, name)
+            if e is None:
+                continue
+            if st["exit"][i] != e:
+                wrong.append((c["key"], name, "exit", st["exit"][i], e))
+                continue
+            b = g.expected(c, name, g.best)
+            if b is not None and e in ("accepted", "overwritten", "rot_removed"):
+                got = st["best"][i][1]
+                if g.fname[got] != b:
+                    wrong.append((c["key"], name, "best", g.fname[got], b))
+            if gname != "real" and st["level"][i] is not None and st["level"][i] != g.qs[i]["level"]:
+                wrong.append((c["key"], name, "level", st["level"][i], g.qs[i]["level"]))
+    assert not wrong, wrong
+    assert g.name == "real" or any(e is not None for e in g.expect.values())
+
+
+def _call(gname, key):
+    g = pc.group(gname)
+    for c, F, mps, res, st in py_result(gname):
+        if c["key"] == key:
+            return g, c, F, res, st, {n: i for i, n in enumerate(g.names(c))}
+    raise KeyError(key)
+
+
+def test_projection_cases_grid_edges():
+    """what the grid group is about, from grid_py: the border cells are populated, the three features that round to
+    column 64 / row 48 are in no cell, one cell holds 70 features, x * 0.1f == 10.5 went to column 11"""
+    g = pc.group("grid")
+    F = g.frame()
+    cells = grid_py(F)
+    where = {g.fname[i]: cell for cell, lst in cells.items() for i in lst}
+    assert where["col0"][0] == 0 and where["col1"][0] == 1 and where["col63"][0] == 63 and where["x634_99"][0] == 63
+    assert where["row0"][1] == 0 and where["row1"][1] == 1 and where["row47"][1] == 47 and where["y474_99"][1] == 47
+    assert where["cell_3071"] == (63, 47)
+    for name in ("x635_dropped", "y475_dropped", "x639_9_dropped"):
+        assert name not in where
+    assert f32(f32(635.0) * F.grid_w_inv) == f32(63.5) and f32(f32(475.0) * F.grid_h_inv) == f32(47.5)
+    assert f32(f32(105.0) * F.grid_w_inv) == f32(10.5) and where["half_A"] == (11, 20) and where["half_B"] == (10, 20)
+    assert where["halfy_A"] == (30, 11) and where["halfy_B"] == (30, 10)
+    assert len(cells[(30, 30)]) == 70
+    # the empty returns and the clamps of GetFeaturesInArea, the whole grid, a window of more than 16 cells
+    for key in ("local",):
+        _, c, _, _, st, at = _call("grid", key)
+        for name in ("out_right", "out_left", "out_below", "out_above"):
+            assert st["ncand"][at[name]] == 0
+    g2, c, F2, _, st, at = _call("clamp", "local")
+    for name, (u, v) in (("clamp_right", (700, 200)), ("clamp_left", (-60, 240)), ("clamp_below", (320, 540)),
+                         ("clamp_above", (360, -60))):
+        assert st["uv"][at[name]] == (u, v) and st["radius"][at[name]] == 80 and st["ncand"][at[name]] == 1
+    _, c, _, _, st, at = _call("wide", "keyframe")
+    assert st["radius"][at["wide_0"]] > 640 and st["ncand"][at["wide_0"]] == 4
+    assert [k for _, _, k in st["ranked"][at["wide_0"]]] == [3, 2, 1, 0]  # the cell order against the index order
+    _, c, _, _, st, at = _call("lanes", "sim3")
+    assert [k for _, _, k in st["ranked"][at["lanes_0"]]] == [2, 1, 0]
+
+
+def test_projection_cases_candidate_edges():
+    g, c, F, _, st, at = _call("cand", "fuse")
+    chi = {n: float(st["chi2"][at[n]][0][1]) for n in ("chi2_mono_under", "chi2_mono_over", "chi2_stereo_under",
+                                                     "chi2_stereo_over")}
+    assert 5.9 < chi["chi2_mono_under"] <= 5.99 < chi["chi2_mono_over"] < 6.1
+    assert 7.7 < chi["chi2_stereo_under"] <= 7.8 < chi["chi2_stereo_over"] < 7.9
+    assert pc.INV_SIGMA2[1] != 1
+    i, j = g.fname.index("er_eq_radius"), g.fname.index("er_ulp_over")
+    xr = lambda n: g.qs[at[n]]["xr"]
+    assert f32(xr("er_eq_radius") - F.uright[i]) == 4 and 4 < f32(xr("er_ulp_over") - F.uright[j]) < 4.00002
+    assert F.uright[j] == pc.down(f32(xr("er_ulp_over") - f32(4)))
+    assert F.uright[g.fname.index("ur_zero")] == 0 and F.uright[g.fname.index("ur_minus1")] == -1
+    _, c, _, _, st, at = _call("cand", "local")
+    assert st["ranked"][at["all_256"]] == [] and st["ncand"][at["all_256"]] == 2
+    assert st["second"][at["rival_at_256"]] == (256, -1)
+    # the ratio group: 0.8f * 75 == 60.0f exactly; the second best of the tie cases
+    _, c, _, _, st, at = _call("ratio", "local")
+    assert st["best"][at["ratio_eq"]][0] == 60 and st["second"][at["ratio_eq"]][0] == 75
+    assert st["best"][at["ratio_over"]][0] == 61 and st["second"][at["single"]] == (256, -1)
+    second = lambda n: g2.fname[st["second"][at[n]][1]]
+    g2 = pc.group("ratio")
+    assert second("tie_50_45_50_first") == "tie_50_45_50_first_0"
+    assert second("tie_50_45_50_first_b") == "tie_50_45_50_first_b_0"
+    assert second("tie_50_70_60") == "tie_50_70_60_2" and second("tie_5_5_levels") == "tie_5_5_levels_1"
+    assert st["radius"][at["viewcos_below"]] == 4 and st["radius"][at["viewcos_0998"]] == 2.5
+    _, c, _, _, st2, _ = _call("ratio", "local_th")
+    assert st["radius"][at["th_factor"]] == 4 and 4 < st2["radius"][at["th_factor"]] < 4.001
+
+
+def test_projection_cases_levels_and_front():
+    flags = {}
+    for k in ("last_fwd", "last_bwd", "last_eq_mb", "last_eq_neg_mb", "last_mono"):
+        st = _call("levels", k)[4]
+        flags[k] = (st["forward"], st["backward"], float(st["tlc_z"]))
+    assert flags == {"last_fwd": (True, False, 0.75), "last_bwd": (False, True, -0.75),
+                     "last_eq_mb": (False, False, 0.5), "last_eq_neg_mb": (False, False, -0.5),
+                     "last_mono": (False, False, 0.75)}
+    assert pc.group("levels").frame().b == f32(0.5)
+    g, c, F, _, st, at = _call("front", "keyframe")
+    q = lambda n: g.qs[at[n]]
+    assert st["uv"][at["u_eq_maxx"]][0] == F.max_x and st["uv"][at["v_eq_maxy"]][1] == F.max_y
+    assert q("u_below_0")["u"] < 0 and pc.up(q("u_below_0")["u"]) == 0 and st["uv"][at["u_eq_0"]][0] == 0
+    assert q("behind")["pos"][2] < 0 and st["uv"][at["behind"]] == (300, 100)
+    assert q("dist_eq_min")["dist"] == f32(f32(0.8) * q("dist_eq_min")["min_dist"]) == 9
+    assert q("dist_below_min")["dist"] == pc.down(f32(f32(0.8) * q("dist_below_min")["min_dist"])) == 9
+    assert q("dist_eq_max")["dist"] == f32(f32(1.2) * q("dist_eq_max")["max_dist"]) == 17
+    assert q("dist_above_max")["dist"] == pc.up(f32(f32(1.2) * q("dist_above_max")["max_dist"])) == 19
+    assert _dot3(q("normal_eq_half")["pos"], q("normal_eq_half")["normal"]) == 0.5 * 19
+    assert 1.4999 < _dot3(q("normal_below_half")["pos"], q("normal_below_half")["normal"]) < 0.5 * 3
+    # nScale = -1 before the clamp, inside the distance test, searched at level 0 by all four variants that predict
+    assert pc.raw_scale(q("scale_low")["max_dist"], q("scale_low")["dist"]) == -1
+    assert q("scale_low")["dist"] == f32(f32(1.2) * q("scale_low")["max_dist"])
+    for key in ("keyframe", "sim3", "fuse", "fuse_sim3"):
+        st_k, at_k = _call("front", key)[4], _call("front", key)[5]
+        assert st_k["exit"][at_k["scale_low"]] == "accepted" and st_k["level"][at_k["scale_low"]] == 0
+    assert pc.raw_scale(q("scale_high")["max_dist"], q("scale_high")["dist"]) > 7 and st["level"][at["scale_high"]] == 7
+    e = pc.group("empty")
+    assert e.frame().n == 0 and len(e.qs) > 0
+
+
+def test_projection_cases_arbitration():
+    """the claimed entry really is the loser's best (or second), claimer and loser sit where the case says, the
+    rescan cases have more than four candidates whose first four are taken"""
+    g = pc.group("arb")
+    assert g.frame().n == pc.ARB_N and g.fname.index("idx_last_A") == pc.ARB_N - 1
+    assert g.fname.index("idx_32768_A") == 32768
+    pos = {r["name"]: i for i, r in enumerate(g.qs)}
+    assert (pos["adjacent_claimer"], pos["adjacent_loser"]) == (10, 11)
+    assert (pos["chunk_edge_claimer"], pos["chunk_edge_loser"]) == (63, 64)
+    assert (pos["far_claimer"], pos["far_loser"]) == (5, 200)
+    assert pos["collide_2048_1"] == pos["collide_2048_0"] + 1 and pos["collide_2048_1"] // 64 == pos["collide_2048_0"] // 64
+    assert pos["collide_4096_1"] == pos["collide_4096_0"] + 1 and pos["collide_4096_1"] // 64 == pos["collide_4096_0"] // 64
+    for n, d in (("collide_2048", 2048), ("collide_4096", 4096)):
+        assert g.fname.index(n + "_1") - g.fname.index(n + "_0") == d
+    for key in ("local", "last", "keyframe", "sim3"):
+        _, c, F, (n, m), st, at = _call("arb", key)
+        for i in range(len(at)):  # every query is active: position in the list = position in the device batch
+            assert st["exit"][i] not in ("skipped", "depth", "out_of_image", "dist_range", "view_angle"), (key, i)
+        for loser, claimer, rank in g.pairs:
+            if key != "local" and loser in ("second_claimed_loser", "best_claimed_loser"):  # about the ratio test
+                continue
+            claimed = st["best"][at[claimer]][1]
+            assert st["exit"][at[claimer]] == "accepted" and st["ranked"][at[loser]][rank][2] == claimed, (key, loser)
+            assert claimed in st["occ_seen"][at[loser]], (key, loser)
+        resc = g.rescan + (g.rescan_claiming if key in ("keyframe", "sim3") else [])
+        for name in resc:
+            r = st["ranked"][at[name]]
+            assert len(r) > 4 and all(k in st["occ_seen"][at[name]] for _, _, k in r[:4]), (key, name)
+        occ = g.fname.index("occupied_best")
+        for k in range(3):
+            assert st["ranked"][at["occupied_%d" % k]][0][2] == occ and F.occupied[occ]
+        if key in ("local", "last"):
+            assert m[g.fname.index("noobs_0")] == at["six_noobs_5"] and n == (m >= 0).sum() + 5
+    # the second-entry claim flips a ratio rejection, the best-entry claim causes one (nnratio 0.8)
+    _, c, F, _, st, at = _call("arb", "local")
+    r = st["ranked"][at["second_claimed_loser"]]
+    assert [d for d, _, _ in r] == [50, 55, 90]
+    assert f32(50) > f32(f32(0.8) * f32(55)) and not f32(50) > f32(f32(0.8) * f32(90))
+    r = st["ranked"][at["best_claimed_loser"]]
+    assert [d for d, _, _ in r] == [40, 50, 55]
+    assert not f32(40) > f32(f32(0.8) * f32(50)) and f32(50) > f32(f32(0.8) * f32(55))
+    for nq in (0, 1, 63, 64, 65):
+        assert len(_call("arb", "keyframe_nq%d" % nq)[5]) == nq
+
+
+def test_projection_cases_rotation():
+    g = pc.group("rot")
+    _, c, F, (n, m), st, at = _call("rot", "last_nq30")
+    assert [st["rot"][i][0] for i in range(30)] == [0] * 20 + [5] * 2 + [9] * 2 + [12] * 2 + [1] * 2 + [7, 0]
+    assert st["rot"][26][1] == f32(0.5) and 12 < st["rot"][24][1] < 12.00001  # exactly .5; a negative rot wrapped to 360
+    assert g.qs[0]["angle"] == 0 and np.signbit(g.qs[0]["angle"]) and st["rot"][0][1] == 0  # rot = -0.0
+    assert f32(g.qs[24]["angle"] - F.angle[24]) < 0
+    assert st["hist"][0] == 21 and st["kept_bins"] == [0, -1, -1] and f32(2) < f32(f32(0.1) * f32(21))
+    shared = g.fname.index("shared")
+    # 30 accepted on 29 features; eight in dropped bins of 2 and the discarded writer are subtracted, the later writer of
+    # the shared feature stays counted although the feature is reset
+    assert m[shared] == -2 and n == 30 - 9 and (m >= 0).sum() == 29 - 9
+    hists = {k: _call("rot", "last_nq%d" % k)[4] for k in (20, 21, 22, 23, 24, 26, 28)}
+    assert [h for h in hists[20]["hist"] if h] == [20] and hists[20]["kept_bins"] == [0, -1, -1]  # one bin
+    assert hists[21]["kept_bins"] == [0, -1, -1] and hists[22]["kept_bins"] == [0, 5, -1]  # max2 = 1 and 2 against 2.0f
+    assert hists[23]["kept_bins"] == [0, 5, -1] and hists[24]["kept_bins"] == [0, 5, 9]  # the same for max3
+    assert hists[26]["kept_bins"] == [0, 5, 9] and hists[26]["hist"][12] == 2  # tie: the first index stays
+    assert hists[28]["kept_bins"] == [0, 1, 5] and f32(f32(0.1) * f32(20)) == f32(2)
+    _, c, _, (n, m), st, at = _call("rot", "keyframe_nq30")
+    assert st["exit"][29] == "th_reject" and st["occ_seen"][29] == [shared] and m[shared] == -2
 
 # ------------------------------------------------------------------ Fuse x2 (ORBmatcher.cc:825-1100)
 import ctypes as _C  # noqa: E402
@@ -431,36 +1049,48 @@ def _predict_scale(max_dist, d, F):
     return min(max(n, 0), len(F.scale_factors) - 1)
 
 
-def fuse_py(F, mp, th, R, t, Ow, inv=None, sim3=False):
+def fuse_py(F, mp, th, R, t, Ow, inv=None, sim3=False, stats=None):
     """ORBmatcher::Fuse(pKF, vpMapPoints, th) (ORBmatcher.cc:825-975) or, with sim3, Fuse(pKF, Scw,
     vpPoints, th, vpReplacePoint) (:977-1100): per MapPoint the bestIdx that the reference fuses."""
     g = grid_py(F)
     bits = np.unpackbits(F.desc, axis=1)
     best = np.full(mp.n, -1, np.int32)
+    st = _Stats(mp.n)
+    st.d["chi2"] = [[] for _ in range(mp.n)]  # (idx, e2 * invSigma2) of the candidates that reach the test
     for i in range(mp.n):
-        if mp.skip[i] or mp.bad[i]:
+        if _flag(mp.skip, i) or _flag(mp.bad, i):
+            st.leave(i, "skipped")
             continue
         p = [f32(v) for v in mp.pos[i]]
         pc = _gemm33_fast(R, p, t)
         if pc[2] < f32(0):
+            st.leave(i, "depth")
             continue
         invz = f32(1.0 / float(pc[2])) if sim3 else f32(f32(1) / pc[2])
         u = f32(f32(f32(F.fx) * f32(pc[0] * invz)) + f32(F.cx))
         v = f32(f32(f32(F.fy) * f32(pc[1] * invz)) + f32(F.cy))
         if not (u >= F.min_x and u < F.max_x and v >= F.min_y and v < F.max_y):
+            st.leave(i, "out_of_image")
             continue
         ur = f32(u - f32(f32(F.bf) * invz))
         PO = [f32(p[k] - f32(Ow[k])) for k in range(3)]
         d3 = _norm3(PO)
         if d3 < f32(f32(0.8) * f32(mp.min_dist[i])) or d3 > f32(f32(1.2) * f32(mp.max_dist[i])):
+            st.leave(i, "dist_range")
             continue
         if _dot3(PO, mp.normal[i]) < 0.5 * float(d3):
+            st.leave(i, "view_angle")
             continue
         lvl = _predict_scale(mp.max_dist[i], d3, F)
         rad = f32(f32(th) * f32(F.scale_factors[lvl]))
         qb = np.unpackbits(mp.desc[i])
-        bd, bi = 1 << 30, -1
-        for idx in area_py(F, g, u, v, rad):
+        bd, bi, seen = 1 << 30, -1, []
+        cand = area_py(F, g, u, v, rad)
+        st.search(i, u, v, rad, lvl, len(cand))
+        if not cand:
+            st.leave(i, "no_candidates")
+            continue
+        for pos, idx in enumerate(cand):
             kl = int(F.octave[idx])
             if kl < lvl - 1 or kl > lvl:
                 continue
@@ -469,17 +1099,29 @@ def fuse_py(F, mp, th, R, t, Ow, inv=None, sim3=False):
                 if F.uright is not None and F.uright[idx] >= 0:
                     er = f32(ur - F.uright[idx])
                     e2 = f32(f32(f32(ex * ex) + f32(ey * ey)) + f32(er * er))
+                    st.d["chi2"][i].append((idx, f32(e2 * inv[kl])))
                     if float(f32(e2 * inv[kl])) > 7.8:
                         continue
                 else:
                     e2 = f32(f32(ex * ex) + f32(ey * ey))
+                    st.d["chi2"][i].append((idx, f32(e2 * inv[kl])))
                     if float(f32(e2 * inv[kl])) > 5.99:
                         continue
             dist = int(np.count_nonzero(bits[idx] != qb))
+            if dist < 256:
+                seen.append((dist, pos, idx))
             if dist < bd:
                 bd, bi = dist, idx
+        st.cands(i, seen, np.zeros(F.n, bool))
+        st.d["best"][i] = (bd, bi)
         if bd <= 50:
             best[i] = bi
+            st.leave(i, "accepted")
+        else:
+            st.leave(i, "th_reject")
+    if stats is not None:
+        st.d["any_occ"] = [False] * mp.n
+        stats.update(st.d)
     return int((best >= 0).sum()), best
 
 
