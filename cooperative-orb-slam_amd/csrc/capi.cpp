@@ -1516,28 +1516,6 @@ int wait_call(hipStream_t st, const int32_t* word) {
     return wait_until(st, [word] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) >= 0; });
 }
 
-/* ComputeThreeMaxima (ORBmatcher.cc:1601-1642) of a 30-bin rotation histogram, for the host-side tail of
- * k_bow_small (the same comparisons as match_kernels.hip three_maxima) */
-void three_maxima_host(const int* hist, int keep[3]) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < 30; i++) {
-        const int s = hist[i];
-        if (s > max1) {
-            max3 = max2; max2 = max1; max1 = s;
-            ind3 = ind2; ind2 = ind1; ind1 = i;
-        } else if (s > max2) {
-            max3 = max2; max2 = s;
-            ind3 = ind2; ind2 = i;
-        } else if (s > max3) {
-            max3 = s; ind3 = i;
-        }
-    }
-    const float tenth = 0.1f * (float)max1;
-    if ((float)max2 < tenth) ind2 = ind3 = -1;
-    else if ((float)max3 < tenth) ind3 = -1;
-    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-}
-
 void make_geom(MatchGeom& g, const float F12[9], float ex, float ey, int nlevels, const float* scale,
                const float* sigma2) {
     for (int i = 0; i < 9; i++) g.F[i] = F12[i];
@@ -1833,7 +1811,7 @@ static int small_finish(orbm_ctx* ctx, const uint8_t* hp, size_t o_out, size_t o
             const int na = (int)(done[i] >> 32);
             for (int j = 0; j < na; j++) hist[(acc[tasks[i].q_begin + j] >> 32) & 31]++;
         }
-        three_maxima_host(hist, keep);
+        three_maxima(hist, keep);
     }
     std::fill(out, out + nout, -1);
     int cnt = 0;

@@ -19,11 +19,14 @@
  *   k_rot_slots     its rotation histogram + ComputeThreeMaxima filter and the per-slot count
  * Every received slot is validated on the device before use (header, sizes, counts, CSR
  * bounds); a bad slot yields no matches and raises the matcher's error flag.
+ * The matching rules (distance, epipolar tests, candidate rule, node lookup, rotation filter) are the shared ones
+ * of orb_match_dev.h; the slot kernels add the clamps and flags on what a slot carries.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/orbslam_amd.h"
+#include "orb_match_dev.h"
 #include "orb_slot.h"
 #include "orb_wave.h"
 
@@ -175,22 +178,6 @@ struct SlotGeoms {
     float ex[kMaxSlotsPerLaunch], ey[kMaxSlotsPerLaunch];
 };
 
-/* CheckDistEpipolarLine (ORBmatcher.cc:140-157) with kp1's line (a, b, c) precomputed in the
- * reference's float order; `dsqr < 3.84*sigma2` compared in double */
-__device__ __forceinline__ bool slot_epi_ok(float a, float b, float c, float x2, float y2, float sigma2) {
-    const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, x2), __fmul_rn(b, y2)), c);
-    const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
-    if (den == 0.f) return false;
-    const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-    return (double)dsqr < 3.84 * (double)sigma2;
-}
-
-__device__ __forceinline__ void slot_epi_line(const float* F, float x1, float y1, float* a, float* b, float* c) {
-    *a = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[0]), __fmul_rn(y1, F[3])), F[6]);
-    *b = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[1]), __fmul_rn(y1, F[4])), F[7]);
-    *c = __fadd_rn(__fadd_rn(__fmul_rn(x1, F[2]), __fmul_rn(y1, F[5])), F[8]);
-}
-
 /* ----------------------------------------------------------------------------------- */
 /* BF: 256 threads = 16 candidate slices x 16 queries. Slice k scans the k-th part of     */
 /* every candidate tile with the reference's rule (accept dist <= best after the checks,  */
@@ -237,11 +224,9 @@ __global__ __launch_bounds__(256) void k_tri_slots_bf(const QueryKF q, const uin
     float la = 0.f, lb = 0.f, lc = 0.f;
     bool st1 = false, skip1 = true;
     if (active) {
-        const uint4* d = (const uint4*)(q.desc + (long long)idx1 * 32);
-        const uint4 a0 = d[0], a1 = d[1];
-        qd[0] = a0.x; qd[1] = a0.y; qd[2] = a0.z; qd[3] = a0.w; qd[4] = a1.x; qd[5] = a1.y; qd[6] = a1.z; qd[7] = a1.w;
+        load_desc8(qd, q.desc + (long long)idx1 * 32);
         const float2 p1 = q.kun ? q.kun[idx1] : (float2){q.kps[idx1].x, q.kps[idx1].y};
-        slot_epi_line(G.F[gr], p1.x, p1.y, &la, &lb, &lc);
+        epi_line(G.F[gr], p1.x, p1.y, &la, &lb, &lc);
         st1 = q.uright ? q.uright[idx1] >= 0.f : false;
         skip1 = q.mpf ? (q.mpf[idx1] & 1) != 0 : false;  // GetMapPoint(idx1) != NULL (:699-703)
     } else {
@@ -279,18 +264,10 @@ __global__ __launch_bounds__(256) void k_tri_slots_bf(const QueryKF q, const uin
             for (int j = jb; j < je; j++) {
                 const int fl = s_flag[j];
                 if (fl & 1) continue;  // vbMatched2 is never set; pMP2 != NULL skips (:722-726)
-                const uint4 c0 = s_desc[2 * j], c1 = s_desc[2 * j + 1];
-                const int dist = __popc(qd[0] ^ c0.x) + __popc(qd[1] ^ c0.y) + __popc(qd[2] ^ c0.z) +
-                                 __popc(qd[3] ^ c0.w) + __popc(qd[4] ^ c1.x) + __popc(qd[5] ^ c1.y) +
-                                 __popc(qd[6] ^ c1.z) + __popc(qd[7] ^ c1.w);
-                if (dist > 50 || dist > bestDist) continue;
-                const float x2 = s_x[j], y2 = s_y[j];
-                const int oct2 = s_oct[j];
-                if (!st1 && !(fl & 2)) {  // mono-mono: epipole radius (:743-749)
-                    const float dx = __fsub_rn(ex, x2), dy = __fsub_rn(ey, y2);
-                    if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < s_th100[oct2]) continue;
-                }
-                if (slot_epi_ok(la, lb, lc, x2, y2, s_sig2[oct2])) {
+                const int dist = hamming8(qd, s_desc[2 * j], s_desc[2 * j + 1]);
+                if (tri_accepts(dist, bestDist, !st1 && !(fl & 2), ex, ey, la, lb, lc,
+                                [&] { return make_float2(s_x[j], s_y[j]); }, [&] { return s_th100[s_oct[j]]; },
+                                [&] { return 3.84 * (double)s_sig2[s_oct[j]]; })) {
                     bestIdx2 = t0 + j;
                     bestDist = dist;
                 }
@@ -334,13 +311,8 @@ __global__ __launch_bounds__(64) void k_tri_slots_bow(const QueryKF q, const uin
     if (i >= nfv1) return;
     const int n1 = min(max(*q.count, 0), q.cap);
     const uint32_t node = q.fv_node[i];
-    int lo = 0, hi = s.nfv;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s.fv_node[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= s.nfv || s.fv_node[lo] != node) return;  // not a common node
+    const int lo = find_node(s.fv_node, s.nfv, node);
+    if (lo < 0) return;  // not a common node
     const int cb = min(max(s.fv_off[lo], 0), s.cap);
     const int ce = min(max(s.fv_off[lo + 1], cb), s.cap);
     const int qb = min(max(q.fv_off[i], 0), q.cap);
@@ -354,12 +326,10 @@ __global__ __launch_bounds__(64) void k_tri_slots_bow(const QueryKF q, const uin
         if (q.mpf && (q.mpf[idx1] & 1)) continue;  // :699-703
         const bool st1 = q.uright ? q.uright[idx1] >= 0.f : false;
         uint32_t qd[8];
-        const uint4* d = (const uint4*)(q.desc + (long long)idx1 * 32);
-        const uint4 a0 = d[0], a1 = d[1];
-        qd[0] = a0.x; qd[1] = a0.y; qd[2] = a0.z; qd[3] = a0.w; qd[4] = a1.x; qd[5] = a1.y; qd[6] = a1.z; qd[7] = a1.w;
+        load_desc8(qd, q.desc + (long long)idx1 * 32);
         const float2 p1 = q.kun ? q.kun[idx1] : (float2){q.kps[idx1].x, q.kps[idx1].y};
         float la, lb, lc;
-        slot_epi_line(F, p1.x, p1.y, &la, &lb, &lc);
+        epi_line(F, p1.x, p1.y, &la, &lb, &lc);
         int bestDist = 50, bestIdx2 = -1;
         for (int ci = cb; ci < ce; ci++) {
             const int idx2 = s.fv_feat[ci];
@@ -369,18 +339,10 @@ __global__ __launch_bounds__(64) void k_tri_slots_bow(const QueryKF q, const uin
             if ((unsigned)oct2 >= (unsigned)s.nlev) { atomicOr(err, 4); continue; }  // as orbx_slot_parse
             const bool st2 = s.uright[idx2] >= 0.f;
             const uint4* cd = (const uint4*)(s.desc + (long long)idx2 * 32);
-            const uint4 c0 = cd[0], c1 = cd[1];
-            const int dist = __popc(qd[0] ^ c0.x) + __popc(qd[1] ^ c0.y) + __popc(qd[2] ^ c0.z) +
-                             __popc(qd[3] ^ c0.w) + __popc(qd[4] ^ c1.x) + __popc(qd[5] ^ c1.y) +
-                             __popc(qd[6] ^ c1.z) + __popc(qd[7] ^ c1.w);
-            if (dist > 50 || dist > bestDist) continue;
-            const float2 p2 = s.kun[idx2];
-            if (!st1 && !st2) {
-                const float dx = __fsub_rn(ex, p2.x), dy = __fsub_rn(ey, p2.y);
-                if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < __fmul_rn(100.f, s.meta->mvScaleFactors[oct2]))
-                    continue;
-            }
-            if (slot_epi_ok(la, lb, lc, p2.x, p2.y, s.meta->mvLevelSigma2[oct2])) {
+            const int dist = hamming8(qd, cd[0], cd[1]);
+            if (tri_accepts(dist, bestDist, !st1 && !st2, ex, ey, la, lb, lc, [&] { return s.kun[idx2]; },
+                            [&] { return __fmul_rn(100.f, s.meta->mvScaleFactors[oct2]); },
+                            [&] { return 3.84 * (double)s.meta->mvLevelSigma2[oct2]; })) {
                 bestIdx2 = idx2;
                 bestDist = dist;
             }
@@ -404,8 +366,6 @@ __global__ __launch_bounds__(64) void k_tri_slots_bow(const QueryKF q, const uin
 /* minimum and runner-up merge by two wave minima of (dist << 16 | position).                  */
 /* match[r*cap1 + idx1] = the slot keyframe's feature idx2 (preset to -1 by the caller).       */
 /* ----------------------------------------------------------------------------------- */
-__device__ __forceinline__ uint32_t rl(uint32_t v, int t) { return (uint32_t)__builtin_amdgcn_readlane((int)v, t); }
-
 __global__ __launch_bounds__(64) void k_bow_slots(const QueryKF q, const uint8_t* __restrict__ slots, long long slot_bytes,
                                                   int slot0, float nnratio, int lds_cap, int32_t* __restrict__ match,
                                                   int32_t* __restrict__ err) {
@@ -422,13 +382,8 @@ __global__ __launch_bounds__(64) void k_bow_slots(const QueryKF q, const uint8_t
     if (i == 0 && lane == 0 && nfv1 > (int)gridDim.x) atomicOr(err, 2);  // query nodes past max_nodes
     if (i >= nfv1) return;
     const uint32_t node = q.fv_node[i];
-    int lo = 0, hi = s.nfv;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (s.fv_node[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= s.nfv || s.fv_node[lo] != node) return;  // not a common node
+    const int lo = find_node(s.fv_node, s.nfv, node);
+    if (lo < 0) return;  // not a common node
     const int cb = min(max(s.fv_off[lo], 0), s.cap);
     const int ce = min(max(s.fv_off[lo + 1], cb), s.cap);
     const int nc = ce - cb;
@@ -457,7 +412,7 @@ __global__ __launch_bounds__(64) void k_bow_slots(const QueryKF q, const uint8_t
     for (int q0 = qb; q0 < qe; q0 += 64) {
         // this lane's query of the next 64: feature index (-1: no good MapPoint, :558-562) and descriptor
         int idx1 = -1;
-        uint4 a0 = make_uint4(0, 0, 0, 0), a1 = a0;
+        uint32_t qdw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (q0 + lane < qe) {
             idx1 = q.fv_feat[q0 + lane];
             if ((unsigned)idx1 >= (unsigned)n1) {
@@ -466,23 +421,19 @@ __global__ __launch_bounds__(64) void k_bow_slots(const QueryKF q, const uint8_t
             } else if (!q.mpf || (q.mpf[idx1] & 3) != 1) {
                 idx1 = -1;
             } else {
-                const uint4* d = (const uint4*)(q.desc + (long long)idx1 * 32);
-                a0 = d[0];
-                a1 = d[1];
+                load_desc8(qdw, q.desc + (long long)idx1 * 32);
             }
         }
         const int nq = min(64, qe - q0);
         for (int t = 0; t < nq; t++) {  // the node's queries in order (wave-uniform)
-            const int i1 = (int)rl((uint32_t)idx1, t);
+            const int i1 = __builtin_amdgcn_readlane(idx1, t);
             if (i1 < 0) continue;
-            const uint32_t x0 = rl(a0.x, t), x1 = rl(a0.y, t), x2 = rl(a0.z, t), x3 = rl(a0.w, t);
-            const uint32_t x4 = rl(a1.x, t), x5 = rl(a1.y, t), x6 = rl(a1.z, t), x7 = rl(a1.w, t);
+            uint32_t x[8];
+            load_desc8_lane(x, qdw, t);
             int b1 = 256, j1 = -1, b2 = 256;
             for (int j = lane; j < nc; j += 64) {
                 if (s_ci[j] < 0) continue;
-                const uint4 c0 = s_cd[2 * j], c1 = s_cd[2 * j + 1];
-                const int dist = __popc(x0 ^ c0.x) + __popc(x1 ^ c0.y) + __popc(x2 ^ c0.z) + __popc(x3 ^ c0.w) +
-                                 __popc(x4 ^ c1.x) + __popc(x5 ^ c1.y) + __popc(x6 ^ c1.z) + __popc(x7 ^ c1.w);
+                const int dist = hamming8(x, s_cd[2 * j], s_cd[2 * j + 1]);
                 if (dist < b1) {
                     b2 = b1;
                     b1 = dist;
@@ -517,51 +468,18 @@ __global__ __launch_bounds__(64) void k_bow_slots(const QueryKF q, const uint8_t
 __global__ __launch_bounds__(256) void k_rot_slots(const QueryKF q, const uint8_t* __restrict__ slots,
                                                    long long slot_bytes, int slot0, int check_ori,
                                                    int32_t* __restrict__ match, int32_t* __restrict__ nmatches) {
-    __shared__ int hist[32];
+    __shared__ int hist[30];
     __shared__ int keep[3];
-    const int r = slot0 + blockIdx.x, tid = threadIdx.x;
+    const int r = slot0 + blockIdx.x;
     SlotRef s;
     if (!slot_open(slots + (long long)r * slot_bytes, slot_bytes, s)) return;  // flagged by k_bow_slots
     const int n1 = min(max(*q.count, 0), q.cap);
     int32_t* m = match + (long long)r * q.cap;
-    auto bin_of = [&](int i, int j) {
-        float rot = __fsub_rn(q.kps[i].angle, s.kps[j].angle);  // vKeysUn angle = vKeys angle
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        const int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        return bin == 30 ? 0 : bin;
-    };
-    if (tid < 32) hist[tid] = 0;
-    __syncthreads();
-    if (check_ori) {
-        for (int i = tid; i < n1; i += 256)
-            if (m[i] >= 0) atomicAdd(&hist[bin_of(i, m[i])], 1);
-        __syncthreads();
-        if (tid == 0) {
-            int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-            for (int b = 0; b < 30; b++) {
-                const int v = hist[b];
-                if (v > max1) { max3 = max2; max2 = max1; max1 = v; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (v > max2) { max3 = max2; max2 = v; ind3 = ind2; ind2 = b; }
-                else if (v > max3) { max3 = v; ind3 = b; }
-            }
-            if (max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-            else if (max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-            keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
-        }
-        __syncthreads();
-    }
     int local = 0;
-    for (int i = tid; i < n1; i += 256) {
-        const int j = m[i];
-        if (j < 0) continue;
-        if (check_ori) {
-            const int bin = bin_of(i, j);
-            if (bin != keep[0] && bin != keep[1] && bin != keep[2]) {
-                m[i] = -1;
-                continue;
-            }
-        }
-        local++;
+    if (check_ori) {  // vKeysUn angle = vKeys angle
+        local = rot_filter_rows(n1, m, [&](int i, int j) { return rot_bin(q.kps[i].angle, s.kps[j].angle); }, hist, keep);
+    } else {
+        for (int i = threadIdx.x; i < n1; i += 256) local += m[i] >= 0;
     }
     if (local) atomicAdd(&nmatches[r], local);
 }

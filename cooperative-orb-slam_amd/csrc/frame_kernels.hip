@@ -35,12 +35,15 @@
  *              MapPoints: one wave per MapPoint, row i of the Hamming distance matrix in LDS,
  *              its median (sorted element floor(0.5*(N-1))) by a 9-bit ballot radix select,
  *              first strict minimum of the medians.
+ * The Hamming distance, the rotation bin and ComputeThreeMaxima are the matcher kernels' shared ones
+ * (orb_match_dev.h, orb_match.h).
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/orbslam_amd.h"
 #include "orb_frame.h"
+#include "orb_match_dev.h"
 #include "orb_wave.h"
 
 namespace orbamd {
@@ -252,9 +255,7 @@ __global__ __launch_bounds__(kStereoThreads) void k_stereo(StereoArgs a, const i
                 }
 #pragma unroll
                 for (int k = 0; k < 4; k++) {
-                    const int dist = __popc(q0.x ^ cv0[k].x) + __popc(q0.y ^ cv0[k].y) + __popc(q0.z ^ cv0[k].z) +
-                                     __popc(q0.w ^ cv0[k].w) + __popc(q1.x ^ cv1[k].x) + __popc(q1.y ^ cv1[k].y) +
-                                     __popc(q1.z ^ cv1[k].z) + __popc(q1.w ^ cv1[k].w);
+                    const int dist = hamming8(q0, q1, cv0[k], cv1[k]);
                     const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)ir[k];
                     if (ok[k] && dist < 100 && key < best) {  // TH_HIGH
                         best = key;
@@ -612,10 +613,7 @@ __device__ __forceinline__ int proj_scan(const ProjCall& c, const ProjQuery& q, 
                     if ((double)__fmul_rn(e2, c.inv_sigma2[oct]) > (urf >= 0 ? 7.8 : 5.99)) continue;
                 }
                 const uint4* fd = (const uint4*)(c.desc + (long long)idx * 32);
-                const uint4 f0 = fd[0], f1 = fd[1];
-                const int dist = __popc(qd0.x ^ f0.x) + __popc(qd0.y ^ f0.y) + __popc(qd0.z ^ f0.z) +
-                                 __popc(qd0.w ^ f0.w) + __popc(qd1.x ^ f1.x) + __popc(qd1.y ^ f1.y) +
-                                 __popc(qd1.z ^ f1.z) + __popc(qd1.w ^ f1.w);
+                const int dist = hamming8(qd0, qd1, fd[0], fd[1]);
                 if (dist < 256 && elig(idx, dist)) {  // bestDist starts at 256 (ORBmatcher.cc:78, 349, 1397, 1550)
                     topk_insert<K>(((unsigned long long)dist << 40) | ((unsigned long long)k << 20) |
                                        ((unsigned long long)idx << 4) | (unsigned)oct, top);
@@ -726,14 +724,6 @@ __device__ __forceinline__ bool proj_accept(const ProjCall& c, unsigned long lon
         if (level == level2 && (float)dist > __fmul_rn(c.nnratio, (float)dist2)) return false;
     }
     return true;
-}
-
-__device__ __forceinline__ int rot_bin(float a1, float a2) {  // ORBmatcher.cc:1423-1430
-    float rot = __fsub_rn(a1, a2);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-    if (bin == 30) bin = 0;
-    return min(max(bin, 0), 29);
 }
 
 constexpr int kProjMaxFeatures = 65536;
@@ -906,24 +896,8 @@ __global__ __launch_bounds__(64) void k_proj_resolve(const ProjCall* __restrict_
     if (c.check_ori) {  // rotation consistency (ORBmatcher.cc:1437-1467)
         rot_bins(c, lane, s_hist);
         wave_lds_sync();
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;  // ComputeThreeMaxima (:1601-1642)
-        for (int i = 0; i < 30; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) {
-                max3 = max2; max2 = max1; max1 = sz;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2; max2 = sz;
-                ind3 = ind2; ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz; ind3 = i;
-            }
-        }
-        if (max2 < __fmul_rn(0.1f, (float)max1)) {
-            ind2 = -1; ind3 = -1;
-        } else if (max3 < __fmul_rn(0.1f, (float)max1)) {
-            ind3 = -1;
-        }
+        int keep[3];
+        three_maxima(s_hist, keep);
         int removed = 0;
         for (int q0 = 0; q0 < c.nq; q0 += 64 * kQU) {  // kQU queries per lane, their loads in flight together
             int f[kQU], b[kQU];
@@ -935,7 +909,7 @@ __global__ __launch_bounds__(64) void k_proj_resolve(const ProjCall* __restrict_
             }
 #pragma unroll
             for (int u = 0; u < kQU; u++)
-                if (q0 + 64 * u + lane < c.nq && f[u] >= 0 && b[u] != ind1 && b[u] != ind2 && b[u] != ind3) {
+                if (q0 + 64 * u + lane < c.nq && f[u] >= 0 && b[u] != keep[0] && b[u] != keep[1] && b[u] != keep[2]) {
                     c.match[f[u]] = -2;
                     removed++;
                 }
@@ -1060,24 +1034,8 @@ __global__ __launch_bounds__(64) void k_init_resolve(const ProjCall* __restrict_
     if (c.check_ori) {  // every accept is in its bin, stolen ones too (:482); ComputeThreeMaxima (:1601-1642)
         rot_bins(c, lane, s_hist);
         wave_lds_sync();
-        int ind1 = -1, ind2 = -1, ind3 = -1, max1 = 0, max2 = 0, max3 = 0;
-        for (int i = 0; i < 30; i++) {
-            const int sz = s_hist[i];
-            if (sz > max1) {
-                max3 = max2; max2 = max1; max1 = sz;
-                ind3 = ind2; ind2 = ind1; ind1 = i;
-            } else if (sz > max2) {
-                max3 = max2; max2 = sz;
-                ind3 = ind2; ind2 = i;
-            } else if (sz > max3) {
-                max3 = sz; ind3 = i;
-            }
-        }
-        if (max2 < __fmul_rn(0.1f, (float)max1)) {
-            ind2 = -1; ind3 = -1;
-        } else if (max3 < __fmul_rn(0.1f, (float)max1)) {
-            ind3 = -1;
-        }
+        int keep[3];
+        three_maxima(s_hist, keep);
         for (int q0 = 0; q0 < c.nq; q0 += 64 * kQU) {  // :497-510 (a stolen i1 is already -1)
             int f[kQU], b[kQU], src[kQU];
 #pragma unroll
@@ -1089,7 +1047,7 @@ __global__ __launch_bounds__(64) void k_init_resolve(const ProjCall* __restrict_
             }
 #pragma unroll
             for (int u = 0; u < kQU; u++)
-                if (q0 + 64 * u + lane < c.nq && f[u] >= 0 && b[u] != ind1 && b[u] != ind2 && b[u] != ind3)
+                if (q0 + 64 * u + lane < c.nq && f[u] >= 0 && b[u] != keep[0] && b[u] != keep[1] && b[u] != keep[2])
                     s_v12[src[u]] = -1;
         }
         wave_lds_sync();
@@ -1126,9 +1084,7 @@ constexpr int kDistinctMaxObs = 1024;
 constexpr int kDistinctWaves = 4;
 
 __device__ __forceinline__ int desc_dist(const uint4 q0, const uint4 q1, const uint8_t* dj) {
-    const uint4 c0 = ((const uint4*)dj)[0], c1 = ((const uint4*)dj)[1];
-    return __popc(q0.x ^ c0.x) + __popc(q0.y ^ c0.y) + __popc(q0.z ^ c0.z) + __popc(q0.w ^ c0.w) +
-           __popc(q1.x ^ c1.x) + __popc(q1.y ^ c1.y) + __popc(q1.z ^ c1.z) + __popc(q1.w ^ c1.w);
+    return hamming8(q0, q1, ((const uint4*)dj)[0], ((const uint4*)dj)[1]);
 }
 
 __global__ __launch_bounds__(64 * kDistinctWaves) void k_distinctive(int npoints, const int32_t* __restrict__ off,

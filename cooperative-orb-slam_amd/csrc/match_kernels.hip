@@ -13,7 +13,8 @@
  *                     (ORBmatcher.cc:159-288, 522-655).
  *   k_rot_filter      rotation-histogram consistency + ComputeThreeMaxima
  *                     (ORBmatcher.cc:236-246, 267-285, 1601-1642).
- * Candidate order / tie rules are the reference's (DESIGN.md "Matcher semantics").
+ * Candidate order / tie rules are the reference's (DESIGN.md "Matcher semantics"); each rule is stated once, in
+ * orb_match_dev.h (ComputeThreeMaxima: orb_match.h), and the kernels here keep their loops, staging and merges.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,28 +22,12 @@
 
 #include "../../include/orbslam_amd.h"
 #include "orb_match.h"
+#include "orb_match_dev.h"
 #include "orb_wave.h"
 
 namespace orbamd {
 
-__device__ __forceinline__ int hamming8(const uint32_t* a, const uint32_t* b) {
-    int d = 0;
-#pragma unroll
-    for (int k = 0; k < 8; k++) d += __popc(a[k] ^ b[k]);
-    return d;
-}
-
-/* CheckDistEpipolarLine (ORBmatcher.cc:140-157) with the line (a,b,c) of kp1 precomputed
- * (same float ops); compare in double like `dsqr < 3.84*sigma2`. */
-__device__ __forceinline__ bool epi_ok(float a, float b, float c, float x2, float y2, double th384) {
-    const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, x2), __fmul_rn(b, y2)), c);
-    const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
-    if (den == 0.f) return false;
-    const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-    return (double)dsqr < th384;
-}
-
-/* the same test against the float threshold thf = 3.84*sigma2 rounded up to a float (MatchGeom::th384f):
+/* epi_ok (orb_match_dev.h) against the float threshold thf = 3.84*sigma2 rounded up to a float (MatchGeom::th384f):
  * for a float dsqr, (double)dsqr < th384 <=> dsqr < thf, so the comparison is exact; thf < 0 rejects */
 __device__ __forceinline__ bool epi_ok_f(float a, float b, float c, float x2, float y2, float thf) {
     const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, x2), __fmul_rn(b, y2)), c);
@@ -52,16 +37,12 @@ __device__ __forceinline__ bool epi_ok_f(float a, float b, float c, float x2, fl
     return dsqr < thf;
 }
 
+/* MatchGeom forms of orb_match_dev.h's epi_line / near_epipole / tri_accepts: per-octave thresholds from the tables */
 __device__ __forceinline__ void epi_line(const MatchGeom& g, float x1, float y1, float* a, float* b, float* c) {
-    *a = __fadd_rn(__fadd_rn(__fmul_rn(x1, g.F[0]), __fmul_rn(y1, g.F[3])), g.F[6]);
-    *b = __fadd_rn(__fadd_rn(__fmul_rn(x1, g.F[1]), __fmul_rn(y1, g.F[4])), g.F[7]);
-    *c = __fadd_rn(__fadd_rn(__fmul_rn(x1, g.F[2]), __fmul_rn(y1, g.F[5])), g.F[8]);
+    epi_line(g.F, x1, y1, a, b, c);
 }
-
-/* epipole-radius rejection for mono-mono pairs (ORBmatcher.cc:743-749) */
 __device__ __forceinline__ bool near_epipole(const MatchGeom& g, float x2, float y2, int oct2) {
-    const float dx = __fsub_rn(g.ex, x2), dy = __fsub_rn(g.ey, y2);
-    return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < g.th100[oct2];
+    return near_epipole(g.ex, g.ey, x2, y2, g.th100[oct2]);
 }
 
 /* Pair p: KF1 = (kps1, desc1, n1), KF2 = (kps2, desc2, n2) resolved by the caller-side
@@ -278,27 +259,9 @@ __global__ __launch_bounds__(kMfThreads) ORBX_MF_ATTR void k_tri_mfma(const int3
     tri_mfma_body_fp4<STEREO>(s, g, match12 + (long long)p * kp_stride, nmatches + p, only_stereo);
 }
 
-/* rotation bin of a match (ORBmatcher.cc:236-246): rot = angA[a] - angB[b], (a,b) = (i, j) or,
- * with swap, (j, i) */
+/* rotation bin of a match: rot = angA[a] - angB[b], (a,b) = (i, j) or, with swap, (j, i) */
 __device__ __forceinline__ int rot_bin(const float* angA, const float* angB, int i, int j, int swap) {
-    float rot = swap ? __fsub_rn(angA[j], angB[i]) : __fsub_rn(angA[i], angB[j]);
-    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-    int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-    return bin == 30 ? 0 : bin;
-}
-
-/* ComputeThreeMaxima (ORBmatcher.cc:1601-1642) over a 30-bin histogram, by one thread */
-__device__ __forceinline__ void three_maxima(const int* hist, int* keep) {
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int i = 0; i < 30; i++) {
-        const int s = hist[i];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-        else if (s > max3) { max3 = s; ind3 = i; }
-    }
-    if (max2 < __fmul_rn(0.1f, (float)max1)) { ind2 = -1; ind3 = -1; }
-    else if (max3 < __fmul_rn(0.1f, (float)max1)) { ind3 = -1; }
-    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+    return swap ? rot_bin(angA[j], angB[i]) : rot_bin(angA[i], angB[j]);
 }
 
 /* Single host-API call (k_tri_nodes / k_bow), one launch: every accepted match is appended to a
@@ -385,9 +348,7 @@ __global__ __launch_bounds__(256) void k_tri_nodes(const DevView v1, const DevVi
     uint32_t q[8];
     float a = 0.f, b = 0.f, c = 0.f;
     if (active) {
-        const uint4* qd = (const uint4*)(v1.desc + (long long)idx1 * 32);
-        const uint4 qa = qd[0], qb = qd[1];
-        q[0] = qa.x; q[1] = qa.y; q[2] = qa.z; q[3] = qa.w; q[4] = qb.x; q[5] = qb.y; q[6] = qb.z; q[7] = qb.w;
+        load_desc8(q, v1.desc + (long long)idx1 * 32);
         epi_line(g, v1.x[idx1], v1.y[idx1], &a, &b, &c);
     }
     int bestDist = 50, bestPos = -1, bestIdx2 = -1;  // TH_LOW (ORBmatcher.cc:704)
@@ -411,14 +372,10 @@ __global__ __launch_bounds__(256) void k_tri_nodes(const DevView v1, const DevVi
         for (int j = part; j < nt; j += 4) {
             const int oc = s_oct[j];
             if (oc < 0) continue;
-            const uint4 c0 = s_d[2 * j], c1 = s_d[2 * j + 1];
-            const int dist = __popc(q[0] ^ c0.x) + __popc(q[1] ^ c0.y) + __popc(q[2] ^ c0.z) + __popc(q[3] ^ c0.w) +
-                             __popc(q[4] ^ c1.x) + __popc(q[5] ^ c1.y) + __popc(q[6] ^ c1.z) + __popc(q[7] ^ c1.w);
-            if (dist > 50 || dist > bestDist) continue;
-            const float x2 = s_x[j], y2 = s_y[j];
-            const int oct2 = oc & 0xFF;
-            if (!st1 && !(oc & 0x100) && near_epipole(g, x2, y2, oct2)) continue;  // ORBmatcher.cc:743-749
-            if (epi_ok(a, b, c, x2, y2, g.th384[oct2])) {
+            const int dist = hamming8(q, s_d[2 * j], s_d[2 * j + 1]);
+            if (tri_accepts(dist, bestDist, !st1 && !(oc & 0x100), g.ex, g.ey, a, b, c,
+                            [&] { return make_float2(s_x[j], s_y[j]); }, [&] { return g.th100[oc & 0xFF]; },
+                            [&] { return g.th384[oc & 0xFF]; })) {
                 bestDist = dist;
                 bestPos = cb + j;
                 bestIdx2 = s_idx[j];
@@ -463,13 +420,8 @@ __global__ __launch_bounds__(64) void k_tri_nodes_pairs(const int32_t* __restric
     if (i >= nfv[f1]) return;
     const uint32_t* nodes2 = fv_node + (long long)f2 * kp_stride;
     const uint32_t node = fv_node[(long long)f1 * kp_stride + i];
-    int lo = 0, hi = nfv[f2];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (nodes2[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= nfv[f2] || nodes2[lo] != node) return;  // not a common node: its queries stay -1
+    const int lo = find_node(nodes2, nfv[f2], node);
+    if (lo < 0) return;  // not a common node: its queries stay -1
     const int32_t* off1 = fv_off + (long long)f1 * (kp_stride + 1);
     const int32_t* off2 = fv_off + (long long)f2 * (kp_stride + 1);
     const int32_t* feat1 = fv_feat + (long long)f1 * kp_stride;
@@ -482,9 +434,7 @@ __global__ __launch_bounds__(64) void k_tri_nodes_pairs(const int32_t* __restric
     for (int qi = off1[i] + (int)threadIdx.x; qi < off1[i + 1]; qi += 64) {
         const int idx1 = feat1[qi];
         uint32_t q[8];
-        const uint4* qd = (const uint4*)(d1 + (long long)idx1 * 32);
-        const uint4 qa = qd[0], qb = qd[1];
-        q[0] = qa.x; q[1] = qa.y; q[2] = qa.z; q[3] = qa.w; q[4] = qb.x; q[5] = qb.y; q[6] = qb.z; q[7] = qb.w;
+        load_desc8(q, d1 + (long long)idx1 * 32);
         const orbx_kp kp1 = k1[idx1];
         float a, b, c;
         epi_line(g, kp1.x, kp1.y, &a, &b, &c);
@@ -492,10 +442,10 @@ __global__ __launch_bounds__(64) void k_tri_nodes_pairs(const int32_t* __restric
         for (int ci = cb; ci < ce; ci++) {
             const int idx2 = feat2[ci];
             const int dist = hamming8(q, (const uint32_t*)(d2 + (long long)idx2 * 32));
-            if (dist > 50 || dist > bestDist) continue;
-            const orbx_kp kp2 = k2[idx2];
-            if (near_epipole(g, kp2.x, kp2.y, kp2.octave)) continue;  // mono-mono (:743-749)
-            if (epi_ok(a, b, c, kp2.x, kp2.y, g.th384[kp2.octave])) {
+            orbx_kp kp2;  // read for a candidate that passes the distance test; every keypoint monocular
+            if (tri_accepts(dist, bestDist, true, g.ex, g.ey, a, b, c,
+                            [&] { kp2 = k2[idx2]; return make_float2(kp2.x, kp2.y); },
+                            [&] { return g.th100[kp2.octave]; }, [&] { return g.th384[kp2.octave]; })) {
                 bestIdx2 = idx2;
                 bestDist = dist;
             }
@@ -514,20 +464,13 @@ __global__ __launch_bounds__(64) void k_tri_nodes_pairs(const int32_t* __restric
 /* mode 1 = (KF,KF): accept best1 < TH_LOW, both sides need a good MapPoint.             */
 /* out[idx of the side that is marked] as in the reference (F index / idx1).            */
 /* ----------------------------------------------------------------------------------- */
-struct Top2 { int b1, i1, b2; };
-__device__ __forceinline__ Top2 top2_merge(Top2 A, Top2 B) {
-    Top2 r;
-    const bool takeB = (B.b1 < A.b1) || (B.b1 == A.b1 && B.i1 >= 0 && (A.i1 < 0 || B.i1 < A.i1));
-    r.b1 = takeB ? B.b1 : A.b1;
-    r.i1 = takeB ? B.i1 : A.i1;
-    r.b2 = min(max(A.b1, B.b1), min(A.b2, B.b2));
-    return r;
-}
-
+/* (Top2 / top2_scan / top2_wave, bow_accepts and the two greedy walks: orb_match_dev.h)         */
 
 /* STAGED (node of <= kBowStage candidates, the common case: ~10 per node at levelsup 4): the node's
  * candidate descriptors and eligibility and, 64 at a time, its queries' descriptors are staged in LDS
- * first, so the greedy loop over queries runs without a global-load round trip per query */
+ * first, so the greedy loop over queries runs without a global-load round trip per query; a node of <= 64
+ * candidates keeps them in registers, one per lane (bow_greedy_lanes). The unstaged form is
+ * bow_greedy_scan over global memory. */
 constexpr int kBowStage = 512;
 
 template <bool STAGED>
@@ -543,21 +486,32 @@ __global__ __launch_bounds__(64) void k_bow(const DevView vq, const DevView vc, 
     const NodeTask t = tasks[blockIdx.x];
     const int lane = threadIdx.x;
     const int nc = t.c_end - t.c_begin;
-    uint8_t* mflag = STAGED ? s_cm : matched;
-    if (STAGED && nc <= 64) {
-        // candidate j = lane, its descriptor in registers; query k's descriptor broadcast by readlane. Per
-        // query: best1 = the first strict minimum = min over eligible lanes of dist << 6 | j; best2 = min dist
-        // of the other eligible lanes (ORBmatcher.cc:205-225); a claimed candidate drops out of its lane
-        // (vpMapPointMatches / vbMatched2 within the node). The greedy chain never leaves registers.
+    auto good = [](const DevView& v, int idx) { return (v.has_mp && v.has_mp[idx]) && !(v.mp_bad && v.mp_bad[idx]); };
+    // a chunk's accepts, emitted together after it (global atomics): the greedy chain waits for no global round trip
+    auto emit_chunk = [&](int na) {
+        if (lane < na) {
+            const int2 a = s_acc[lane];
+            if (mode == 0) call_emit(tail, a.y, a.x);  // vpMapPointMatches[bestIdxF] = pMP(KF idx)
+            else call_emit(tail, a.x, a.y);            // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
+        }
+        __syncthreads();  // s_qi / s_qd / s_acc are rewritten by the next chunk
+    };
+    if (!STAGED) {
+        bow_greedy_scan(lane, vq.node_feat + t.q_begin, t.q_end - t.q_begin, vq.desc, vc.node_feat + t.c_begin, nc,
+                        vc.desc, matched, mode, nnratio, [&](int idx) { return good(vq, idx); },
+                        [&](int idx) { return good(vc, idx); },
+                        [&](int idxq, int idxc) {
+                            if (mode == 0) call_emit(tail, idxc, idxq);  // vpMapPointMatches[bestIdxF] = pMP(KF idx)
+                            else call_emit(tail, idxq, idxc);            // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
+                        });
+    } else if (nc <= 64) {
         uint32_t cdw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         bool elig = false;
         int idxc = -1;
         if (lane < nc) {
             idxc = vc.node_feat[t.c_begin + lane];
-            const uint4* cd = (const uint4*)(vc.desc + (long long)idxc * 32);
-            const uint4 a = cd[0], b = cd[1];
-            cdw[0] = a.x; cdw[1] = a.y; cdw[2] = a.z; cdw[3] = a.w; cdw[4] = b.x; cdw[5] = b.y; cdw[6] = b.z; cdw[7] = b.w;
-            elig = mode == 0 || ((vc.has_mp && vc.has_mp[idxc]) && !(vc.mp_bad && vc.mp_bad[idxc]));
+            load_desc8(cdw, vc.desc + (long long)idxc * 32);
+            elig = mode == 0 || good(vc, idxc);
         }
         for (int qb = t.q_begin; qb < t.q_end; qb += 64) {
             const int nq = min(64, t.q_end - qb);
@@ -565,148 +519,64 @@ __global__ __launch_bounds__(64) void k_bow(const DevView vq, const DevView vc, 
             uint32_t qdw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
             if (lane < nq) {
                 const int iq = vq.node_feat[qb + lane];
-                const bool ok = (vq.has_mp && vq.has_mp[iq]) && !(vq.mp_bad && vq.mp_bad[iq]);
-                myq = ok ? iq : -1;
-                const uint4* qd = (const uint4*)(vq.desc + (long long)iq * 32);
-                const uint4 a = qd[0], b = qd[1];
-                qdw[0] = a.x; qdw[1] = a.y; qdw[2] = a.z; qdw[3] = a.w; qdw[4] = b.x; qdw[5] = b.y; qdw[6] = b.z; qdw[7] = b.w;
+                myq = good(vq, iq) ? iq : -1;
+                load_desc8(qdw, vq.desc + (long long)iq * 32);
             }
-            int na = 0;
-            for (int k = 0; k < nq; k++) {
-                const int idxq = __builtin_amdgcn_readlane(myq, k);
-                if (idxq < 0) continue;  // no good MapPoint (uniform)
-                int dist = 0;
-#pragma unroll
-                for (int u = 0; u < 8; u++) dist += __popc(cdw[u] ^ (uint32_t)__builtin_amdgcn_readlane((int)qdw[u], k));
-                const uint32_t m1 = wave_min_u32(elig ? ((uint32_t)dist << 6 | (uint32_t)lane) : 0xFFFFFFFFu);
-                if (m1 == 0xFFFFFFFFu) continue;  // no eligible candidate left
-                const int i1 = (int)(m1 & 63u), b1 = (int)(m1 >> 6);
-                const int b2 = (int)wave_min_u32((elig && lane != i1) ? (uint32_t)dist : 256u);
-                const bool ok_th = mode == 0 ? (b1 <= 50) : (b1 < 50);  // TH_LOW (ORBmatcher.cc:228 / :598)
-                if (ok_th && __fmul_rn(1.0f, (float)b1) < __fmul_rn(nnratio, (float)b2)) {
-                    const int idxc_w = __builtin_amdgcn_readlane(idxc, i1);
-                    if (lane == i1) elig = false;
-                    if (lane == 0) s_acc[na] = make_int2(idxq, idxc_w);
-                    na++;
-                }
-            }
+            const int na = bow_greedy_lanes(lane, nq, myq, qdw, cdw, idxc, elig, mode, nnratio, 0,
+                                            [&](int n, int idxq, int idxc_w, int, int) {
+                                                if (lane == 0) s_acc[n] = make_int2(idxq, idxc_w);
+                                            });
             __syncthreads();
-            if (lane < na) {
-                const int2 a = s_acc[lane];
-                if (mode == 0) call_emit(tail, a.y, a.x);  // vpMapPointMatches[bestIdxF] = pMP(KF idx)
-                else call_emit(tail, a.x, a.y);            // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
+            emit_chunk(na);
+        }
+    } else {
+        // a chunk's queries: index (-1 = no good MapPoint) and descriptor; the first chunk is loaded together
+        // with the candidates (one dependent load pair instead of two before the greedy loop)
+        auto load_queries = [&](int qb) {
+            if (lane < min(64, t.q_end - qb)) {
+                const int idxq = vq.node_feat[qb + lane];
+                s_qi[lane] = good(vq, idxq) ? idxq : -1;
+                const uint4* qd = (const uint4*)(vq.desc + (long long)idxq * 32);
+                s_qd[2 * lane] = qd[0];
+                s_qd[2 * lane + 1] = qd[1];
             }
-            __syncthreads();
-        }
-        call_tail(tail);
-        return;
-    }
-    // STAGED: a chunk's queries: index (-1 = no good MapPoint) and descriptor; the first chunk is loaded
-    // together with the candidates (one dependent load pair instead of two before the greedy loop)
-    auto load_queries = [&](int qb) {
-        if (lane < min(64, t.q_end - qb)) {
-            const int idxq = vq.node_feat[qb + lane];
-            const bool ok = (vq.has_mp && vq.has_mp[idxq]) && !(vq.mp_bad && vq.mp_bad[idxq]);
-            s_qi[lane] = ok ? idxq : -1;
-            const uint4* qd = (const uint4*)(vq.desc + (long long)idxq * 32);
-            s_qd[2 * lane] = qd[0];
-            s_qd[2 * lane + 1] = qd[1];
-        }
-    };
-    if (STAGED) load_queries(t.q_begin);
-    for (int j = lane; j < nc; j += 64) {
-        mflag[j] = 0;
-        if (STAGED) {
+        };
+        load_queries(t.q_begin);
+        for (int j = lane; j < nc; j += 64) {
             const int idxc = vc.node_feat[t.c_begin + j];
             const uint4* cd = (const uint4*)(vc.desc + (long long)idxc * 32);
+            s_cm[j] = 0;
             s_cd[2 * j] = cd[0];
             s_cd[2 * j + 1] = cd[1];
-            s_cok[j] = mode == 0 || ((vc.has_mp && vc.has_mp[idxc]) && !(vc.mp_bad && vc.mp_bad[idxc]));
+            s_cok[j] = mode == 0 || good(vc, idxc);
             s_cidx[j] = idxc;
         }
-    }
-    __syncthreads();
-    for (int qb = t.q_begin; qb < t.q_end; qb += 64) {
-        const int nq = min(64, t.q_end - qb);
-        int na = 0;  // STAGED: accepts of this chunk, emitted together after it
-        if (STAGED && qb != t.q_begin) {
-            load_queries(qb);
-            __syncthreads();
-        }
-        for (int k = 0; k < nq; k++) {
-            int idxq;
-            uint32_t q[8];
-            if (STAGED) {
-                idxq = s_qi[k];
+        __syncthreads();
+        for (int qb = t.q_begin; qb < t.q_end; qb += 64) {
+            const int nq = min(64, t.q_end - qb);
+            int na = 0;
+            if (qb != t.q_begin) {
+                load_queries(qb);
+                __syncthreads();
+            }
+            for (int k = 0; k < nq; k++) {
+                const int idxq = s_qi[k];
                 if (idxq < 0) continue;
-                const uint4 a0 = s_qd[2 * k], a1 = s_qd[2 * k + 1];
-                q[0] = a0.x; q[1] = a0.y; q[2] = a0.z; q[3] = a0.w; q[4] = a1.x; q[5] = a1.y; q[6] = a1.z; q[7] = a1.w;
-            } else {
-                idxq = vq.node_feat[qb + k];
-                if (!(vq.has_mp && vq.has_mp[idxq])) continue;
-                if (vq.mp_bad && vq.mp_bad[idxq]) continue;
-                const uint32_t* qd = (const uint32_t*)(vq.desc + (long long)idxq * 32);
-#pragma unroll
-                for (int u = 0; u < 8; u++) q[u] = qd[u];
-            }
-            Top2 r = {256, -1, 256};
-            for (int j = lane; j < nc; j += 64) {
-                if (mflag[j]) continue;
-                int dist;
-                if (STAGED) {
-                    if (!s_cok[j]) continue;
-                    const uint4 c0 = s_cd[2 * j], c1 = s_cd[2 * j + 1];
-                    dist = __popc(q[0] ^ c0.x) + __popc(q[1] ^ c0.y) + __popc(q[2] ^ c0.z) + __popc(q[3] ^ c0.w) +
-                           __popc(q[4] ^ c1.x) + __popc(q[5] ^ c1.y) + __popc(q[6] ^ c1.z) + __popc(q[7] ^ c1.w);
-                } else {
-                    const int idxc = vc.node_feat[t.c_begin + j];
-                    if (mode == 1) {
-                        if (!(vc.has_mp && vc.has_mp[idxc])) continue;
-                        if (vc.mp_bad && vc.mp_bad[idxc]) continue;
-                    }
-                    dist = hamming8(q, (const uint32_t*)(vc.desc + (long long)idxc * 32));
-                }
-                if (dist < r.b1) { r.b2 = r.b1; r.b1 = dist; r.i1 = j; }
-                else if (dist < r.b2) { r.b2 = dist; }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                Top2 o2;
-                o2.b1 = __shfl_xor(r.b1, o, 64);
-                o2.i1 = __shfl_xor(r.i1, o, 64);
-                o2.b2 = __shfl_xor(r.b2, o, 64);
-                r = top2_merge(r, o2);
-            }
-            const bool ok_th = mode == 0 ? (r.b1 <= 50) : (r.b1 < 50);
-            if (ok_th && r.i1 >= 0 && __fmul_rn(1.0f, (float)r.b1) < __fmul_rn(nnratio, (float)r.b2)) {
-                if (STAGED) {
-                    // the greedy chain touches LDS only: the match is recorded here and emitted (global
-                    // atomics) after the chunk, so no accept waits for a global round trip
+                uint32_t q[8];
+                load_desc8(q, s_qd + 2 * k);
+                const Top2 r = top2_wave(top2_scan(lane, nc, [&](int j) {
+                    return s_cm[j] || !s_cok[j] ? -1 : hamming8(q, s_cd[2 * j], s_cd[2 * j + 1]);
+                }));
+                if (r.i1 >= 0 && bow_accepts(r.b1, r.b2, mode, nnratio)) {
                     if (lane == 0) {
-                        mflag[r.i1] = 1;
+                        s_cm[r.i1] = 1;
                         s_acc[na] = make_int2(idxq, s_cidx[r.i1]);
                     }
                     na++;
                     __syncthreads();
-                } else {
-                    const int idxc = vc.node_feat[t.c_begin + r.i1];
-                    __syncthreads();
-                    if (lane == 0) {
-                        mflag[r.i1] = 1;
-                        if (mode == 0) call_emit(tail, idxc, idxq);  // vpMapPointMatches[bestIdxF] = pMP(KF idx)
-                        else call_emit(tail, idxq, idxc);            // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
-                    }
-                    __syncthreads();
                 }
             }
-        }
-        if (STAGED) {
-            if (lane < na) {
-                const int2 a = s_acc[lane];
-                if (mode == 0) call_emit(tail, a.y, a.x);  // vpMapPointMatches[bestIdxF] = pMP(KF idx)
-                else call_emit(tail, a.x, a.y);            // vpMatches12[idx1] = vpMapPoints2[bestIdx2]
-            }
-            __syncthreads();  // s_qi / s_qd / s_acc are rewritten by the next chunk
+            emit_chunk(na);
         }
     }
     call_tail(tail);
@@ -733,8 +603,7 @@ __global__ __launch_bounds__(64) void k_bow_small(const BowSmall a) {
     float cang = 0.f;
     if (lane < nc) {
         const int p = t.c_begin + lane;
-        const uint4 x0 = a.cd[2 * p], x1 = a.cd[2 * p + 1];
-        cdw[0] = x0.x; cdw[1] = x0.y; cdw[2] = x0.z; cdw[3] = x0.w; cdw[4] = x1.x; cdw[5] = x1.y; cdw[6] = x1.z; cdw[7] = x1.w;
+        load_desc8(cdw, a.cd + 2 * p);
         idxc = a.cf[p];
         cang = a.ca[p * a.ca_stride];
         elig = a.mode == 0 || ((a.cgood[p >> 5] >> (p & 31)) & 1u);
@@ -747,40 +616,18 @@ __global__ __launch_bounds__(64) void k_bow_small(const BowSmall a) {
         uint32_t qdw[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (lane < nq) {
             const int p = qb + lane;
-            const uint4 x0 = a.qd[2 * p], x1 = a.qd[2 * p + 1];
-            qdw[0] = x0.x; qdw[1] = x0.y; qdw[2] = x0.z; qdw[3] = x0.w; qdw[4] = x1.x; qdw[5] = x1.y; qdw[6] = x1.z; qdw[7] = x1.w;
+            load_desc8(qdw, a.qd + 2 * p);
             myq = ((a.qgood[p >> 5] >> (p & 31)) & 1u) ? a.qf[p] : -1;
             qang = a.qa[p * a.qa_stride];
         }
-        for (int k = 0; k < nq; k++) {
-            const int idxq = __builtin_amdgcn_readlane(myq, k);
-            if (idxq < 0) continue;  // no good MapPoint (uniform)
-            int dist = 0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) dist += __popc(cdw[u] ^ (uint32_t)__builtin_amdgcn_readlane((int)qdw[u], k));
-            const uint32_t m1 = wave_min_u32(elig ? ((uint32_t)dist << 6 | (uint32_t)lane) : 0xFFFFFFFFu);
-            if (m1 == 0xFFFFFFFFu) continue;  // no eligible candidate left
-            const int i1 = (int)(m1 & 63u), b1 = (int)(m1 >> 6);
-            const int b2 = (int)wave_min_u32((elig && lane != i1) ? (uint32_t)dist : 256u);
-            const bool ok_th = a.mode == 0 ? (b1 <= 50) : (b1 < 50);  // TH_LOW (ORBmatcher.cc:228 / :598)
-            if (ok_th && __fmul_rn(1.0f, (float)b1) < __fmul_rn(a.nnratio, (float)b2)) {
-                const int idxc_w = __builtin_amdgcn_readlane(idxc, i1);
-                int bin = 0;
-                if (a.check_ori) {  // rot = angle(KF / KF1 keypoint) - angle(F / KF2 keypoint) in both modes
-                    const float qa_k = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, qang), k));
-                    const float ca_i = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, cang), i1));
-                    float rot = __fsub_rn(qa_k, ca_i);
-                    if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-                    bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-                    if (bin == 30) bin = 0;
-                }
-                if (lane == i1) elig = false;
-                if (lane == 0)
-                    small_emit(a.out + t.q_begin + na, a.mode == 0 ? idxc_w : idxq, a.mode == 0 ? idxq : idxc_w, bin,
-                               a.seq);
-                na++;
-            }
-        }
+        na = bow_greedy_lanes(lane, nq, myq, qdw, cdw, idxc, elig, a.mode, a.nnratio, na,
+                              [&](int n, int idxq, int idxc_w, int k, int i1) {
+                                  // rot = angle(KF / KF1 keypoint) - angle(F / KF2 keypoint) in both modes
+                                  const int bin = a.check_ori ? rot_bin(readlane_f(qang, k), readlane_f(cang, i1)) : 0;
+                                  if (lane == 0)
+                                      small_emit(a.out + t.q_begin + n, a.mode == 0 ? idxc_w : idxq,
+                                                 a.mode == 0 ? idxq : idxc_w, bin, a.seq);
+                              });
     }
     if (lane == 0)
         __hip_atomic_store(a.done + blockIdx.x, (unsigned long long)(uint32_t)a.seq | (unsigned long long)na << 32,
@@ -793,10 +640,6 @@ __global__ __launch_bounds__(64) void k_bow_small(const BowSmall a) {
  * 704-776: skip a MapPoint / non-stereo candidate, dist > TH_LOW or > best; epipole radius for mono pairs;
  * CheckDistEpipolarLine; accept = new best, ties to the later). Accepts are compacted by ballot into host
  * memory, then the chunk's done word; the rotation histogram is the host's. */
-__device__ __forceinline__ float readlane_f(float v, int l) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), l));
-}
-
 __global__ __launch_bounds__(64) void k_tri_small(const TriSmall a) {
     const SmallTask t = a.tasks[blockIdx.x];
     const int lane = threadIdx.x;
@@ -806,8 +649,7 @@ __global__ __launch_bounds__(64) void k_tri_small(const TriSmall a) {
     float ea = 0.f, eb = 0.f, ec = 0.f, ang1 = 0.f;
     uint32_t q[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (p1 < t.q_end) {
-        const uint4 x0 = a.qd[2 * p1], x1 = a.qd[2 * p1 + 1];
-        q[0] = x0.x; q[1] = x0.y; q[2] = x0.z; q[3] = x0.w; q[4] = x1.x; q[5] = x1.y; q[6] = x1.z; q[7] = x1.w;
+        load_desc8(q, a.qd + 2 * p1);
         const NodeRec r = a.qr[p1];
         idx1 = a.qf[p1];
         st1 = a.q_ur && (r.oct & 0x100);
@@ -824,8 +666,7 @@ __global__ __launch_bounds__(64) void k_tri_small(const TriSmall a) {
         float cx = 0.f, cy = 0.f, cang = 0.f;
         if (lane < nt) {
             const int p2 = cb + lane;
-            const uint4 x0 = a.cd[2 * p2], x1 = a.cd[2 * p2 + 1];
-            cdw[0] = x0.x; cdw[1] = x0.y; cdw[2] = x0.z; cdw[3] = x0.w; cdw[4] = x1.x; cdw[5] = x1.y; cdw[6] = x1.z; cdw[7] = x1.w;
+            load_desc8(cdw, a.cd + 2 * p2);
             const NodeRec r = a.cr[p2];
             cidx = a.cf[p2];
             const bool st2 = a.c_ur && (r.oct & 0x100);
@@ -838,15 +679,12 @@ __global__ __launch_bounds__(64) void k_tri_small(const TriSmall a) {
         for (int j = 0; j < nt; j++) {
             const int oc = __builtin_amdgcn_readlane(coct, j);
             if (oc < 0) continue;  // a MapPoint (or mono in stereo mode): uniform
-            int dist = 0;
-#pragma unroll
-            for (int u = 0; u < 8; u++) dist += __popc(q[u] ^ (uint32_t)__builtin_amdgcn_readlane((int)cdw[u], j));
+            const int dist = hamming8_lane(q, cdw, j);
             const float x2 = readlane_f(cx, j), y2 = readlane_f(cy, j), a2 = readlane_f(cang, j);
             const int i2 = __builtin_amdgcn_readlane(cidx, j);
-            if (!active || dist > 50 || dist > bestDist) continue;
-            const int oct2 = oc & 0xFF;
-            if (!st1 && !(oc & 0x100) && near_epipole(a.g, x2, y2, oct2)) continue;  // ORBmatcher.cc:743-749
-            if (epi_ok(ea, eb, ec, x2, y2, a.g.th384[oct2])) {
+            if (active && tri_accepts(dist, bestDist, !st1 && !(oc & 0x100), a.g.ex, a.g.ey, ea, eb, ec,
+                                      [&] { return make_float2(x2, y2); }, [&] { return a.g.th100[oc & 0xFF]; },
+                                      [&] { return a.g.th384[oc & 0xFF]; })) {
                 bestDist = dist;
                 bestIdx2 = i2;
                 bestAng = a2;
@@ -854,13 +692,7 @@ __global__ __launch_bounds__(64) void k_tri_small(const TriSmall a) {
         }
     }
     const bool acc = active && bestIdx2 >= 0;
-    int bin = 0;
-    if (acc && a.check_ori) {  // rot = kp1.angle - kp2.angle (ORBmatcher.cc:784-792)
-        float rot = __fsub_rn(ang1, bestAng);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        if (bin == 30) bin = 0;
-    }
+    const int bin = acc && a.check_ori ? rot_bin(ang1, bestAng) : 0;  // rot = kp1.angle - kp2.angle (:784-792)
     const unsigned long long m = __ballot(acc);
     const int rank = __popcll(m & ((1ull << lane) - 1ull));
     if (acc) small_emit(a.out + t.q_begin + rank, idx1, bestIdx2, bin, a.seq);
@@ -888,13 +720,8 @@ __global__ __launch_bounds__(64) void k_bow_pairs(const int32_t* __restrict__ qf
     if (i >= nfv[fq]) return;
     const uint32_t* nodes_c = fv_node + (long long)fc * kp_stride;
     const uint32_t node = fv_node[(long long)fq * kp_stride + i];
-    int lo = 0, hi = nfv[fc];
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (nodes_c[mid] < node) lo = mid + 1;
-        else hi = mid;
-    }
-    if (lo >= nfv[fc] || nodes_c[lo] != node) return;
+    const int lo = find_node(nodes_c, nfv[fc], node);
+    if (lo < 0) return;
     const int32_t* offq = fv_off + (long long)fq * (kp_stride + 1);
     const int32_t* offc = fv_off + (long long)fc * (kp_stride + 1);
     const int32_t* featq = fv_feat + (long long)fq * kp_stride;
@@ -904,46 +731,14 @@ __global__ __launch_bounds__(64) void k_bow_pairs(const int32_t* __restrict__ qf
     const uint8_t* dq = desc + (long long)fq * kp_stride * 32;
     const uint8_t* dc = desc + (long long)fc * kp_stride * 32;
     int32_t* o = out + (long long)p * kp_stride;
-    const int lane = threadIdx.x;
-    const int nc = offc[lo + 1] - offc[lo];
-    for (int j = lane; j < nc; j += 64) matched[j] = 0;
-    __syncthreads();
-    for (int i1 = offq[i]; i1 < offq[i + 1]; i1++) {
-        const int idxq = featq[i1];
-        if ((fq_flags[idxq] & 3) != 1) continue;  // a good MapPoint
-        const uint32_t* qd = (const uint32_t*)(dq + (long long)idxq * 32);
-        uint32_t q[8];
-#pragma unroll
-        for (int k = 0; k < 8; k++) q[k] = qd[k];
-        Top2 r = {256, -1, 256};
-        for (int j = lane; j < nc; j += 64) {
-            if (matched[j]) continue;
-            const int idxc = featc[j];
-            if (mode == 1 && (fc_flags[idxc] & 3) != 1) continue;
-            const int dist = hamming8(q, (const uint32_t*)(dc + (long long)idxc * 32));
-            if (dist < r.b1) { r.b2 = r.b1; r.b1 = dist; r.i1 = j; }
-            else if (dist < r.b2) { r.b2 = dist; }
-        }
-#pragma unroll
-        for (int sh = 32; sh > 0; sh >>= 1) {
-            Top2 o2;
-            o2.b1 = __shfl_xor(r.b1, sh, 64);
-            o2.i1 = __shfl_xor(r.i1, sh, 64);
-            o2.b2 = __shfl_xor(r.b2, sh, 64);
-            r = top2_merge(r, o2);
-        }
-        const bool ok_th = mode == 0 ? (r.b1 <= 50) : (r.b1 < 50);
-        if (ok_th && r.i1 >= 0 && __fmul_rn(1.0f, (float)r.b1) < __fmul_rn(nnratio, (float)r.b2)) {
-            const int idxc = featc[r.i1];
-            __syncthreads();
-            if (lane == 0) {
-                matched[r.i1] = 1;
-                if (mode == 0) o[idxc] = idxq;
-                else o[idxq] = idxc;
-            }
-            __syncthreads();
-        }
-    }
+    auto good = [](const uint8_t* flags, int idx) { return (flags[idx] & 3) == 1; };  // a MapPoint, not bad
+    bow_greedy_scan(threadIdx.x, featq + offq[i], offq[i + 1] - offq[i], dq, featc, offc[lo + 1] - offc[lo], dc, matched,
+                    mode, nnratio, [&](int idx) { return good(fq_flags, idx); },
+                    [&](int idx) { return good(fc_flags, idx); },
+                    [&](int idxq, int idxc) {
+                        if (mode == 0) o[idxc] = idxq;
+                        else o[idxq] = idxc;
+                    });
 }
 
 /* per-pair count of out >= 0 (after the optional rotation filter) */
@@ -955,29 +750,13 @@ __global__ __launch_bounds__(256) void k_count_pairs(const int32_t* __restrict__
     atomicAdd(&nmatches[p], local);
 }
 
-/* Rotation consistency (ORBmatcher.cc:236-246 + 267-285): entries i with m[i] >= 0; rot =
+/* Rotation consistency (ORBmatcher.cc:236-246 + 267-285, rot_filter_rows): entries i with m[i] >= 0; rot =
  * angA[a] - angB[b] where (a,b) = (i, m[i]) or, with swap, (m[i], i). One workgroup. */
 __global__ __launch_bounds__(256) void k_rot_filter(int n, int32_t* __restrict__ m, const float* __restrict__ angA,
                                                     const float* __restrict__ angB, int swap, int32_t* __restrict__ nout) {
     __shared__ int hist[30];
     __shared__ int keep[3];
-    if (threadIdx.x < 30) hist[threadIdx.x] = 0;
-    __syncthreads();
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int j = m[i];
-        if (j >= 0) atomicAdd(&hist[rot_bin(angA, angB, i, j, swap)], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) three_maxima(hist, keep);
-    __syncthreads();
-    int local = 0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int j = m[i];
-        if (j < 0) continue;
-        const int bin = rot_bin(angA, angB, i, j, swap);
-        if (bin != keep[0] && bin != keep[1] && bin != keep[2]) m[i] = -1;
-        else local++;
-    }
+    const int local = rot_filter_rows(n, m, [&](int i, int j) { return rot_bin(angA, angB, i, j, swap); }, hist, keep);
     if (nout) atomicAdd(nout, local);
 }
 
@@ -991,34 +770,10 @@ __global__ __launch_bounds__(256) void k_rot_filter_pairs(const int32_t* __restr
     const int p = blockIdx.x;
     const orbx_kp* k1 = kps + (long long)q1[p] * kp_stride;
     const orbx_kp* k2 = kps + (long long)q2[p] * kp_stride;
-    int32_t* m = match12 + (long long)p * kp_stride;
-    const int n = counts[q1[p]];
-    if (threadIdx.x < 30) hist[threadIdx.x] = 0;
-    __syncthreads();
-    auto bin_of = [&](int i, int j) {
-        float rot = swap ? __fsub_rn(k2[j].angle, k1[i].angle) : __fsub_rn(k1[i].angle, k2[j].angle);
-        if (rot < 0.0f) rot = __fadd_rn(rot, 360.0f);
-        const int bin = (int)roundf(__fmul_rn(rot, 1.0f / 30));
-        return bin == 30 ? 0 : bin;
-    };
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int j = m[i];
-        if (j >= 0) atomicAdd(&hist[bin_of(i, j)], 1);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        three_maxima(hist, keep);
-        nmatches[p] = 0;
-    }
-    __syncthreads();
-    int local = 0;
-    for (int i = threadIdx.x; i < n; i += 256) {
-        const int j = m[i];
-        if (j < 0) continue;
-        const int bin = bin_of(i, j);
-        if (bin != keep[0] && bin != keep[1] && bin != keep[2]) m[i] = -1;
-        else local++;
-    }
+    if (threadIdx.x == 0) nmatches[p] = 0;  // the filter's barriers order it before every thread's add
+    const int local = rot_filter_rows(counts[q1[p]], match12 + (long long)p * kp_stride, [&](int i, int j) {
+        return swap ? rot_bin(k2[j].angle, k1[i].angle) : rot_bin(k1[i].angle, k2[j].angle);
+    }, hist, keep);
     atomicAdd(&nmatches[p], local);
 }
 

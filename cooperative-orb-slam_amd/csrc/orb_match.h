@@ -1,5 +1,6 @@
 /*
- * orb_match.h -- matcher argument structs shared by capi.cpp and match_kernels.hip.
+ * orb_match.h -- matcher argument structs shared by capi.cpp and match_kernels.hip, and ComputeThreeMaxima for
+ * both sides. The matcher's device-side rules are in orb_match_dev.h.
  */
 #pragma once
 #include <stdint.h>
@@ -16,6 +17,22 @@ struct MatchGeom {
     double th384[16];
     float th384f[16];  // th384 rounded up to a float: (double)d < th384 <=> d < th384f for a float d
 };
+
+/* ComputeThreeMaxima (ORBmatcher.cc:1601-1642) over a 30-bin rotation histogram, by one thread: keep[] = the
+ * bins of the three largest counts in the reference's order, -1 for the second / third below a tenth of the first */
+__host__ __device__ inline void three_maxima(const int* hist, int keep[3]) {
+    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+    for (int i = 0; i < 30; i++) {
+        const int s = hist[i];
+        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
+        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
+        else if (s > max3) { max3 = s; ind3 = i; }
+    }
+    const float tenth = 0.1f * (float)max1;  // a lone float product (the build has -ffp-contract=off)
+    if ((float)max2 < tenth) ind2 = ind3 = -1;
+    else if ((float)max3 < tenth) ind3 = -1;
+    keep[0] = ind1; keep[1] = ind2; keep[2] = ind3;
+}
 
 /* device-side copy of an orbm_kf_view */
 struct DevView {

@@ -145,8 +145,33 @@ def _oracle_slot_match(kq, dq, eq, dec, geo, use_bow):
     return oracle_py.search_for_triangulation(vq, vs, F12, ex, ey, False, False)
 
 
-@pytest.mark.parametrize("use_bow", [False, True])
+def _edge_slot_nodes(r, node):
+    """slot r's FeatureVector node ids moved so that the query's ids 100..115 meet the ends of the slot's node
+    search: slot 0 keeps 105 as its first id and moves the others above every query id (the query's 100..104 lie
+    below it, 106..115 between two of its ids); slot 1 keeps 115 as its last id and moves the others below
+    (100..114 lie between two ids); every id of slot 2 lies below the query's (the query id is above them all).
+    The order of the nodes' feature lists is kept (the ids stay ascending)."""
+    node = node.astype(np.int64)
+    if r == 0:
+        lo = node[node < 105] + 100
+        return np.concatenate([node[node == 105], lo, node[node > 105] + 100]).astype(np.uint32), \
+            np.concatenate([np.nonzero(node == 105)[0], np.nonzero(node < 105)[0], np.nonzero(node > 105)[0]])
+    keep = (node == 115) if r == 1 else np.zeros(len(node), bool)
+    return np.where(keep, node, node - 50).astype(np.uint32), np.arange(len(node))
+
+
+def _edge_fv(r, fv):
+    node, off, feat = fv
+    ids, order = _edge_slot_nodes(r, node)
+    feats = [feat[off[i]:off[i + 1]] for i in order]
+    off2 = np.concatenate([[0], np.cumsum([len(f) for f in feats])]).astype(np.int32)
+    return ids, off2, np.concatenate(feats).astype(np.int32)
+
+
+@pytest.mark.parametrize("use_bow", [False, True, "edges"])
 def test_slot_match_equals_oracle(use_bow):
+    """use_bow = "edges": the common-node kernels (k_tri_slots_bow, and k_bow_slots on the same slots) with the
+    common node as the slot's first id, its last id, and query ids between two slot ids or above them all"""
     torch = pytest.importorskip("torch")
     rng = np.random.default_rng(17)
     frames, tabs = _extract(1, 0, n=4)
@@ -164,6 +189,8 @@ def test_slot_match_equals_oracle(use_bow):
         e = _extras(rng, k) if r != 1 else ({"fv": _extras(rng, k)["fv"]} if use_bow else {})  # slot 1 mono
         if "fv" in e:
             e["fv"] = _desc_fv(d)  # node ids shared with the query's (common nodes to match over)
+            if use_bow == "edges":
+                e["fv"] = _edge_fv(r, e["fv"])
         host = exchange.pack_host(_meta(r, tabs), k, d, cap, **e)
         slots[r * host.size:(r + 1) * host.size].copy_(torch.from_numpy(host))
         decs.append(exchange.parse(host))
@@ -194,6 +221,30 @@ def test_slot_match_equals_oracle(use_bow):
         assert np.all(out[r, len(kq):].cpu().numpy() == -1)
         total += no
     assert total > 0
+    if use_bow == "edges":
+        assert int(nm[0].item()) > 0 and int(nm[1].item()) > 0 and int(nm[2].item()) == 0
+        # SearchByBoW(KF,KF) (k_bow_slots) over the same keyframes, every keypoint with a MapPoint (some bad) so
+        # that the single common node carries matches. Slot 1 has no MapPoints (no match whatever its nodes), so
+        # here slot 0 takes the last-id placement and slot 2 the first-id one
+        for r in (0, 2):
+            k, d = frames[1 + r]
+            e = {"mp_flags": decs[r]["mp_flags"] | 1, "fv": _edge_fv(1 if r == 0 else 0, _desc_fv(d))}
+            host = exchange.pack_host(_meta(r, tabs), k, d, cap, **e)
+            slots[r * host.size:(r + 1) * host.size].copy_(torch.from_numpy(host))
+            decs[r] = exchange.parse(host)
+        eq["mp_flags"] = eq["mp_flags"] | 1
+        srcq, keepq = _device_source(torch, kq, dq, eq)
+        for check_ori in (True, False):
+            exchange.bow_slots_device(mh._h, srcq, cap, nref, slots, exchange.slot_bytes(cap), out, nm, 0.75,
+                                      check_ori, max_nodes=len(eq["fv"][0]))
+            torch.cuda.synchronize()
+            assert orbamd.load().orbm_check_error(mh._h, None) == 0
+            for r in range(nref):
+                no, mo = _oracle_slot_bow(kq, dq, eq, decs[r], 0.75, check_ori)
+                np.testing.assert_array_equal(out[r, :len(kq)].cpu().numpy(), mo, err_msg="slot %d" % r)
+                assert int(nm[r].item()) == no and (no > 0) == (r != 1)
+        mh.close()
+        return
     # a corrupt slot (foreign version) in the middle: no matches, error flag, the others unchanged
     bad = slots.clone()
     sb = exchange.slot_bytes(cap)

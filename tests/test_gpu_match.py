@@ -362,3 +362,153 @@ def test_triangulation_bf_stereo_batch(W, H, nf, only_stereo, check_ori):
         np.testing.assert_array_equal(mg, mo, err_msg="pair %d" % b)
         assert int(pipe.nmatch[b].item()) == no and no > 0
     pipe.close()
+
+
+def _sized_featvecs(rng, n1, n2, sizes):
+    """hand-built FeatureVectors: common node k holds sizes[k] = (queries, candidates) features drawn without
+    replacement from each side (a feature sits in one node, as in a DBoW2 FeatureVector)"""
+    assert sum(q for q, _ in sizes) <= n1 and sum(c for _, c in sizes) <= n2
+    p1, p2 = rng.permutation(n1), rng.permutation(n2)
+    fv1, fv2, o1, o2 = {}, {}, 0, 0
+    for k, (q, c) in enumerate(sizes):
+        fv1[50 + 3 * k] = [int(i) for i in p1[o1:o1 + q]]
+        fv2[50 + 3 * k] = [int(i) for i in p2[o2:o2 + c]]
+        o1, o2 = o1 + q, o2 + c
+    return fv1, fv2
+
+
+# every (queries, candidates) combination of the lane-per-candidate chain: 1 / 64 / 65 queries (65 = a second
+# 64-query chunk) over 1 / 63 / 64 candidates
+_SMALL_NODES = [(q, c) for c in (1, 63, 64) for q in (1, 64, 65)]
+BOW_NODE_CASES = {
+    # every node <= 64 candidates: the small-call kernel k_bow_small
+    "small": (1000, _SMALL_NODES),
+    # one node of 65 candidates: k_bow<true>, its staged branch (65) and its lane-per-candidate branch (the rest)
+    "staged": (1000, _SMALL_NODES + [(65, 65)]),
+    # one node of 513 candidates: k_bow<false>. 513 + 512 + 65 + 64 candidates are more than the 1000 features of
+    # the other cases' frames, so this one extracts 2000 from the same 640x480 images
+    "unstaged": (2000, [(65, 513), (64, 64), (1, 65), (65, 512)]),
+}
+
+
+@pytest.mark.parametrize("case", list(BOW_NODE_CASES))
+def test_search_by_bow_node_size_boundaries(case):
+    """SearchByBoW at the node sizes where the host API changes kernel (every node <= 64 candidates: k_bow_small;
+    <= 512: k_bow<true>, whose nodes of <= 64 take the lane-per-candidate chain; above: k_bow<false>), with a node
+    whose queries all lack a good MapPoint and a node whose candidates all do, both modes, rotation on and off"""
+    nf, sizes = BOW_NODE_CASES[case]
+    rng = np.random.default_rng(23 + nf + len(sizes))
+    (k1, d1), (k2, d2) = _frames_kf(2, 9, nf=nf)[0]
+    tabs = _frames_kf(2, 9, 1, nf=nf)[1]
+    sizes = sizes + [(5, 10), (10, 7)]
+    fv1, fv2 = _sized_featvecs(rng, len(k1), len(k2), sizes)
+    mp1, bad1 = rng.random(len(k1)) < 0.8, rng.random(len(k1)) < 0.1
+    mp2, bad2 = rng.random(len(k2)) < 0.8, rng.random(len(k2)) < 0.1
+    no_q, no_c = sorted(fv1)[-2], sorted(fv2)[-1]
+    mp1[fv1[no_q]] = False   # a node whose queries all lack a good MapPoint (half by the bad flag)
+    bad1[fv1[no_q][::2]] = True
+    mp2[fv2[no_c]] = False   # a node whose candidates are all ineligible in (KF,KF) mode
+    bad2[fv2[no_c][::2]] = True
+    v1 = _view(k1, d1, tabs, feat_vec=fv1, has_mp=mp1, mp_bad=bad1)
+    v2 = _view(k2, d2, tabs, feat_vec=fv2, has_mp=mp2, mp_bad=bad2)
+    total = 0
+    for kfkf in (False, True):
+        for ori in (False, True):
+            m = orbamd.ORBmatcher(0.75, ori)
+            ng, mg = m.SearchByBoW(v1, v2, other_is_keyframe=kfkf)
+            no, mo = oracle_py.search_by_bow(v1, v2, 0.75, ori, other_is_keyframe=kfkf)
+            assert ng == no
+            np.testing.assert_array_equal(mg, mo)
+            total += no
+            m.close()
+    assert total > 0
+
+
+def _edge_featvecs(descs):
+    """FeatureVectors of three frames [Z, A, B] that put the common nodes at the ends of the node search. A's ids
+    are 100 + 10 k (k = the top 4 bits of descriptor byte 0); B keeps 100 and 250, moves k = 1..13 to 105 + 10 k
+    (between two of A's ids) and k = 14 to 300 (above every id of A); Z has no node at all. With B as the candidate
+    frame the common node 100 is its first id and A's other ids fall between two of B's; with A as the candidate
+    frame 100 is its first id, 250 its last, 115..235 lie between two of its ids and 300 above all of them."""
+    def fv(d, ids):
+        out = {}
+        for i in range(len(d)):
+            out.setdefault(ids[int(d[i, 0] >> 4)], []).append(i)
+        return out
+    ids_a = [100 + 10 * k for k in range(16)]
+    ids_b = [100] + [105 + 10 * k for k in range(1, 14)] + [300, 250]
+    return [{}, fv(descs[1], ids_a), fv(descs[2], ids_b)]
+
+
+def test_batch_pairs_node_search_edges():
+    """k_tri_nodes_pairs and k_bow_pairs (device FeatureVectors) where the common node is the candidate frame's
+    first or last id, the query id lies between two candidate ids or above them all, and the candidate (or query)
+    frame has no node; the pair lists are no identity, so a swapped frame index shows"""
+    import ctypes as C
+    torch = pytest.importorskip("torch")
+    W, H, B = 640, 480, 3
+    frames = orbamd.synth_frames(1, 7, B, W, H)
+    pipe = orbamd.device.BatchPipeline(torch, W, H, B)
+    pipe.extract(torch.from_numpy(frames).cuda())
+    torch.cuda.synchronize()
+    S = pipe.stride
+    res = [pipe.host_keypoints(b) for b in range(B)]
+    tabs = oracle_py.OracleExtractor(1000, 1.2, 8, 20, 7).tables()
+    fvs = _edge_featvecs([d for _, d in res])
+    fv_node, fv_off = np.zeros((B, S), np.uint32), np.zeros((B, S + 1), np.int32)
+    fv_feat, nfv = np.zeros((B, S), np.int32), np.zeros(B, np.int32)
+    for b in range(B):
+        ids = sorted(fvs[b])
+        feats = [f for i in ids for f in sorted(fvs[b][i])]
+        nfv[b] = len(ids)
+        fv_node[b, :len(ids)] = ids
+        fv_off[b, 1:len(ids) + 1] = np.cumsum([len(fvs[b][i]) for i in ids])
+        fv_feat[b, :len(feats)] = feats
+    pipe.fv_node, pipe.fv_off = torch.from_numpy(fv_node.view(np.int32)).cuda(), torch.from_numpy(fv_off).cuda()
+    pipe.fv_feat, pipe.nfv = torch.from_numpy(fv_feat).cuda(), torch.from_numpy(nfv).cuda()
+    pipe.max_nodes = 16
+    pairs = [(1, 2), (2, 1), (1, 0), (0, 1), (2, 0)]  # (query frame, candidate frame); frame 0 = Z
+    P = len(pairs)
+    qf = torch.tensor([a for a, _ in pairs], dtype=torch.int32).cuda()
+    cf = torch.tensor([b for _, b in pairs], dtype=torch.int32).cuda()
+    out = torch.empty((P, S), dtype=torch.int32).cuda()
+    nm = torch.zeros(P, dtype=torch.int32).cuda()
+    lib = orbamd.load()
+    F = np.ascontiguousarray(pipe.F12.reshape(9))
+    totals = np.zeros(P, np.int64)
+    for check_ori in (False, True):
+        rc = lib.orbm_triangulation_nodes_batch_device(
+            pipe.mh, P, qf.data_ptr(), cf.data_ptr(), pipe.kps.data_ptr(), pipe.desc.data_ptr(),
+            pipe.counts.data_ptr(), S, pipe.fv_node.data_ptr(), pipe.fv_off.data_ptr(), pipe.fv_feat.data_ptr(),
+            pipe.nfv.data_ptr(), pipe.max_nodes, F.ctypes.data, pipe.ex, pipe.ey, len(pipe.scale),
+            pipe.scale.ctypes.data, pipe.sigma2.ctypes.data, int(check_ori), out.data_ptr(), nm.data_ptr(),
+            C.c_void_p(pipe.stream_ptr()))
+        assert rc == 0
+        torch.cuda.synchronize()
+        for p, (a, b) in enumerate(pairs):
+            va = _view(*res[a], tabs, feat_vec=fvs[a])
+            vb = _view(*res[b], tabs, feat_vec=fvs[b])
+            no, mo = oracle_py.search_for_triangulation(va, vb, pipe.F12, pipe.ex, pipe.ey, False, check_ori)
+            np.testing.assert_array_equal(out[p, :va.n].cpu().numpy(), mo, err_msg="tri pair %d" % p)
+            assert int(nm[p].item()) == no
+            totals[p] += no
+    assert totals[0] > 0 and totals[1] > 0 and not totals[2:].any()
+    rng = np.random.default_rng(31)
+    has_mp, bad = rng.random((B, S)) < 0.8, rng.random((B, S)) < 0.1
+    flags = torch.from_numpy((has_mp.astype(np.uint8) | (bad.astype(np.uint8) << 1))).cuda()
+    totals[:] = 0
+    for mode in (1, 0):
+        for ratio, ori in ((0.75, True), (0.6, False)):
+            pipe.search_by_bow_pairs(mode, qf, cf, flags, ratio, ori, out, nm)
+            torch.cuda.synchronize()
+            for p, (a, b) in enumerate(pairs):
+                na, nb = len(res[a][0]), len(res[b][0])
+                va = _view(*res[a], tabs, feat_vec=fvs[a], has_mp=has_mp[a, :na], mp_bad=bad[a, :na])
+                vb = _view(*res[b], tabs, feat_vec=fvs[b], has_mp=has_mp[b, :nb], mp_bad=bad[b, :nb])
+                no, mo = oracle_py.search_by_bow(va, vb, ratio, ori, other_is_keyframe=mode == 1)
+                rows = na if mode == 1 else nb
+                np.testing.assert_array_equal(out[p, :rows].cpu().numpy(), mo, err_msg="bow pair %d" % p)
+                assert int(nm[p].item()) == no
+                totals[p] += no
+    assert totals[0] > 0 and totals[1] > 0 and not totals[2:].any()
+    pipe.close()
