@@ -8,12 +8,12 @@ reference's constructor logic by hand / from its source text:
   level sizes          ORBextractor.cc:1111-1112
 """
 import os
-import re
 
 import numpy as np
 import pytest
 
 import oracle_py
+from extract_py import _decode_header
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -40,14 +40,6 @@ def test_scale_tables_double_member():
         s.append(np.float32(np.float64(s[-1]) * np.float64(np.float32(1.2))))
     assert np.array_equal(t["scale"], np.array(s, np.float32))
     assert np.array_equal(t["sigma2"], (np.array(s, np.float32) * np.array(s, np.float32)).astype(np.float32))
-
-
-def _decode_header(path, name):
-    txt = open(path).read()
-    body = txt[txt.index(name):]
-    body = body[body.index("{") + 1: body.index("}")]
-    vals = [int(v, 16) for v in re.findall(r"0x[0-9a-f]{2}", body)]
-    return np.array(vals, np.uint8).astype(np.int8)
 
 
 def test_pattern_tables_match_reference_hash():
