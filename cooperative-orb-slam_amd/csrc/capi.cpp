@@ -2047,7 +2047,7 @@ int orbm_triangulation_bf_batch_device(orbm_ctx* ctx, int npairs, const int32_t*
                                        const float* scale_factors, const float* level_sigma2, int check_ori,
                                        int32_t* d_match12, int32_t* d_nmatches, void* stream) {
     if (!ctx || npairs < 0 || !F12 || nlevels < 1 || nlevels > 16 || !scale_factors || !level_sigma2 ||
-        kp_stride < 1)
+        kp_stride < 1 || kp_stride > 64 * 1024)  // k_tri_mfma's selection key holds 65535 - idx2 in 16 bits
         return ORBX_EARG;
     if (npairs == 0) return 0;
     HIPR(hipSetDevice(ctx->device));
@@ -2068,7 +2068,7 @@ int orbm_triangulation_bf_stereo_batch_device(orbm_ctx* ctx, int npairs, const i
                                               const float* level_sigma2, int only_stereo, int check_ori,
                                               int32_t* d_match12, int32_t* d_nmatches, void* stream) {
     if (!ctx || npairs < 0 || !F12 || nlevels < 1 || nlevels > 16 || !scale_factors || !level_sigma2 ||
-        kp_stride < 1 || (npairs > 0 && !d_uright))
+        kp_stride < 1 || kp_stride > 64 * 1024 || (npairs > 0 && !d_uright))  // 16-bit index in the selection key
         return ORBX_EARG;
     if (npairs == 0) return 0;
     HIPR(hipSetDevice(ctx->device));

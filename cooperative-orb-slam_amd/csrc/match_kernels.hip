@@ -118,6 +118,10 @@ __device__ __forceinline__ void tri_mfma_body_fp4(const PairSrc& s, const MatchG
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int qblk = blockIdx.x * (32 * kMfWaves);
     if (qblk >= s.n1) return;  // block-uniform
+    if (s.n2 <= 0) {  // empty candidate frame (block-uniform): no row of it exists to load, every query stays unmatched
+        if (tid < 32 * kMfWaves && qblk + tid < s.n1) out[qblk + tid] = -1;
+        return;
+    }
     const int h = lane >> 5;
     const int qi = qblk + wave * 32 + (lane & 31);
     const bool qon = qi < s.n1;

@@ -457,47 +457,7 @@ def _flag(a, i):
     return a is not None and bool(a[i])
 
 
-def _three_maxima_py(sizes):
-    """ORBmatcher::ComputeThreeMaxima (ORBmatcher.cc:1601-1642): the kept bins"""
-    ind, m = [-1, -1, -1], [0, 0, 0]
-    for i, s in enumerate(sizes):
-        if s > m[0]:
-            m, ind = [s, m[0], m[1]], [i, ind[0], ind[1]]
-        elif s > m[1]:
-            m, ind = [m[0], s, m[1]], [ind[0], i, ind[1]]
-        elif s > m[2]:
-            m[2], ind[2] = s, i
-    if f32(m[1]) < f32(f32(0.1) * f32(m[0])):
-        ind[1] = ind[2] = -1
-    elif f32(m[2]) < f32(f32(0.1) * f32(m[0])):
-        ind[2] = -1
-    return ind
-
-
-def _rot_push(hist, st, i, a1, a2, idx):
-    """ORBmatcher.cc:1431-1441 / 1560-1570"""
-    rot = f32(f32(a1) - f32(a2))
-    if rot < 0.0:
-        rot = f32(rot + f32(360.0))
-    p = f32(rot * f32(f32(1.0) / f32(30)))
-    b = int(roundf(p))
-    if b == 30:
-        b = 0
-    assert 0 <= b < 30
-    hist[b].append(idx)
-    st.d["rot"][i] = (b, p)
-
-
-def _rot_filter_py(hist, st, match, nm):
-    """ORBmatcher.cc:1447-1467 / 1577-1596 (-2 stands for the NULL the reference writes)"""
-    keep = _three_maxima_py([len(h) for h in hist])
-    st.d["hist"], st.d["kept_bins"] = [len(h) for h in hist], keep
-    for b in range(30):
-        if b not in keep:
-            for idx in hist[b]:
-                match[idx] = -2
-                nm -= 1
-    return nm
+from match_py import _rot_filter_py, _rot_push, _three_maxima_py  # noqa: E402,F401
 
 
 def last_frame_py(F, Tcw, mp, Tl, th, bmono, check_ori, stats=None):
