@@ -4,6 +4,7 @@ Mirrors the reference's two C++ class surfaces so tests and tools read like ORB-
 
 * :class:`ORBextractor` -- ``ORB_SLAM2::ORBextractor`` (ORBextractor.h:45-111)
 * :class:`ORBmatcher`   -- ``ORB_SLAM2::ORBmatcher`` (ORBmatcher.h:37-102)
+* :class:`KeyFrameDatabase` -- ``ORB_SLAM2::KeyFrameDatabase`` (KeyFrameDatabase.h:42-70)
 
 All compute runs in liborbamd.so (HIP kernels for gfx950) through the C ABI declared in
 include/orbslam_amd.h. There is no CPU fallback: without the library or a GPU the
@@ -16,3 +17,4 @@ from . import device, frame, projection  # noqa: F401
 from .projection import FrameView, MapPoints  # noqa: F401
 from .vocabulary import ORBVocabulary  # noqa: F401
 from .frame import compute_stereo_matches  # noqa: F401
+from .database import KeyFrameDatabase  # noqa: F401

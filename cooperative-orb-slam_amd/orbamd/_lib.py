@@ -180,6 +180,17 @@ SIGNATURES = {
     "orbv_info": (_I, [_P, C.POINTER(_I), C.POINTER(_I), C.POINTER(_I), C.POINTER(_I)]),
     "orbv_transform": (_I, [_P, _P, _I, _I, _P, _P, C.POINTER(_I), _P, _P, _P, C.POINTER(_I)]),
     "orbv_transform_batch_device": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "orbdb_create": (_I, [_I, _I, _I, _I, C.POINTER(_P)]),
+    "orbdb_destroy": (None, [_P]),
+    "orbdb_add": (_I, [_P, C.c_uint64, _P, _P, _I, _P]),
+    "orbdb_add_device": (_I, [_P, C.c_uint64, _P, _P, _P, _P]),
+    "orbdb_erase": (_I, [_P, C.c_uint64, _P]),
+    "orbdb_clear": (_I, [_P, _P]),
+    "orbdb_entries": (_I, [_P, _I, _P, _P, C.POINTER(_I)]),
+    "orbdb_query_device": (_I, [_P, _I, _P, _SZ, _P, _SZ, _P, _SZ, _P, _P, _P, _P]),
+    "orbdb_query": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, C.POINTER(_I), _P]),
+    "orbdb_check_error": (_I, [_P, _P]),
+    "orbdb_select_candidates": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, C.POINTER(_I)]),
     "orbm_compute_distinctive_descriptors_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "orbx_selftest_sincosf": (_I, [_P, _P, _P, _I, _P]),
     "orbx_profile_enable": (_I, [_P, _I]),

@@ -478,6 +478,89 @@ int orbv_transform_batch_device(orbv_handle* h, int nframes, const uint8_t* d_de
                                 int32_t* d_nfv, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Keyframe database -- the scoring half of KeyFrameDatabase (KeyFrameDatabase.cc:33-309): the
+ * BowVectors of every keyframe stay resident in HBM, and one query scores a BowVector against
+ * all of them, replacing the inverted-file walk (KeyFrameDatabase.cc:86-104, 207-222) and the
+ * per-keyframe mpVoc->score calls (:133, :249) of DetectLoopCandidates (called by
+ * LoopClosing::DetectLoop, LoopClosing.cc:143) and DetectRelocalizationCandidates (called by
+ * Tracking::Relocalization, Tracking.cc:1348). Only DBoW2's L1 scoring (ORBvoc.txt's) is
+ * implemented; DBoW2 is not vendored in the reference: L1Scoring::score is restated (parity
+ * unpinned, as for the transform):
+ *     s += (fabs(vi - wi) - fabs(vi)) - fabs(wi)   per common word, ascending word id, double
+ *     score = (float)(-s / 2.0)                    (-0.0f when no word is common)
+ * Entries are identified by a caller-chosen 64-bit key. Every call takes the HIP stream it is
+ * ordered on (0 = the default stream); calls on one database must be ordered by the caller
+ * (one stream, or events between streams). The handle's bookkeeping (key -> entry, free list,
+ * insertion sequence numbers) is thread-safe.
+ * ---------------------------------------------------------------------------------- */
+typedef struct orbdb_handle orbdb_handle;
+#define ORBDB_SCORING_L1 0 /* DBoW2::L1_NORM */
+#define ORBDB_MODE_LOOP 0
+#define ORBDB_MODE_RELOC 1
+#define ORBDB_MAX_WORDS 4096
+
+/* KeyFrameDatabase::KeyFrameDatabase (KeyFrameDatabase.cc:33-37): room for `capacity` keyframes
+ * of at most word_stride (<= 4096) BowVector entries each. scoring other than ORBDB_SCORING_L1:
+ * ORBX_EARG. The device storage is allocated by the first call that needs it (ORBX_EDEVICE there
+ * when the device is unusable). */
+int orbdb_create(int device, int capacity, int word_stride, int scoring, orbdb_handle** out);
+void orbdb_destroy(orbdb_handle* db);
+/* KeyFrameDatabase::add (KeyFrameDatabase.cc:40-46) from host arrays (word ids strictly
+ * ascending, n <= word_stride, else ORBX_EARG; a key already present: ORBX_EARG; no free entry:
+ * ORBX_ECAPACITY). The entry gets the next insertion sequence number. Synchronises `stream`
+ * (the arrays may be released on return). */
+int orbdb_add(orbdb_handle* db, uint64_t key, const uint32_t* words, const double* values, int n,
+              void* stream);
+/* the same from device memory (a slot's BOWWORD / BOWVALUE sections and header nbow in the
+ * all-gather receive buffer, or orbv_transform_batch_device's output), no host copy. The count
+ * and the word order are checked on the device: a bad input leaves an empty entry and raises the
+ * error flag of orbdb_check_error; nothing is read past word_stride entries (which both arrays
+ * must hold when the count is not trusted). */
+int orbdb_add_device(orbdb_handle* db, uint64_t key, const uint32_t* d_words, const double* d_values,
+                     const int32_t* d_count, void* stream);
+/* KeyFrameDatabase::erase (KeyFrameDatabase.cc:48-67; unknown keys are ignored) and clear
+ * (:69-73), ordered on `stream` against the queries queued before them */
+int orbdb_erase(orbdb_handle* db, uint64_t key, void* stream);
+int orbdb_clear(orbdb_handle* db, void* stream);
+/* the live entries in insertion order: keys[i], entry index slots[i] (either may be NULL);
+ * *n = their number (ORBX_ECAPACITY if cap is smaller) */
+int orbdb_entries(orbdb_handle* db, int cap, uint64_t* keys, int32_t* slots, int* n);
+/* nq queries against every entry, enqueued on `stream`. Query q's word ids are at d_words +
+ * q * word_stride_bytes (uint32, ascending), its values at d_values + q * value_stride_bytes
+ * (double), its count at d_counts + q * count_stride_bytes (int32; more than 4096: error flag,
+ * scored as empty) -- so the slots of a receive buffer or the rows of a transform batch are
+ * queried in place. Outputs at [q * capacity + entry index]: d_ncommon (mnLoopWords /
+ * mnRelocWords, KeyFrameDatabase.cc:102, :220; -1 for an entry that is not live), d_score
+ * (mpVoc->score, :133, :249) and d_first_word (the smallest common word id, which orders
+ * lKFsSharingWords, :99, :218; 0xFFFFFFFF if none). */
+int orbdb_query_device(orbdb_handle* db, int nq, const void* d_words, size_t word_stride_bytes,
+                       const void* d_values, size_t value_stride_bytes, const void* d_counts,
+                       size_t count_stride_bytes, int32_t* d_ncommon, float* d_score,
+                       uint32_t* d_first_word, void* stream);
+/* one host query (n <= 4096): uploads it, queries, synchronises `stream` and returns the live
+ * entries in insertion order (*nout of them; ORBX_ECAPACITY if cap is smaller) */
+int orbdb_query(orbdb_handle* db, const uint32_t* words, const double* values, int n, int cap,
+                uint64_t* keys, int32_t* ncommon, float* score, uint32_t* first_word, int* nout,
+                void* stream);
+/* reads and clears the device error flag (synchronises `stream`): ORBX_EDEVICE if a device add
+ * or query since the last call rejected its input */
+int orbdb_check_error(orbdb_handle* db, void* stream);
+/* The candidate selection of DetectLoopCandidates (KeyFrameDatabase.cc:107-196, mode
+ * ORBDB_MODE_LOOP) and DetectRelocalizationCandidates (:224-308, ORBDB_MODE_RELOC) over the n
+ * entries of a query, in insertion order. Host only, no device. connected[i] != 0 (loop mode;
+ * NULL = none): entry i is in pKF->GetConnectedKeyFrames(). Entry i's
+ * GetBestCovisibilityKeyFrames(10) are neigh[neigh_off[i] .. neigh_off[i+1]) as entry indices in
+ * best-covisibility order, -1 for a keyframe that is not in the database. last_score[i] is the
+ * persistent mLoopScore / mRelocScore: written only for the entries the reference scores
+ * (ncommon > minCommonWords), read for the neighbours (in reloc mode also for neighbours that
+ * were not scored by this call, as the reference does). out_idx (n entries) receives the
+ * candidates' entry indices in the reference's order, *nout their number. */
+int orbdb_select_candidates(int mode, int n, const int32_t* ncommon, const float* score,
+                            const uint32_t* first_word, const uint8_t* connected,
+                            const int32_t* neigh_off, const int32_t* neigh, float min_score,
+                            float* last_score, int32_t* out_idx, int* nout);
+
+/* ------------------------------------------------------------------------------------
  * Cross-agent keyframe slot -- replaces the LCM message lcmKeyFrame::lcmKeyFrameInfo
  * (ORB_SLAM2.1/include/lcmKeyFrame/lcmKeyFrameInfo.hpp:24-150), published by the sending
  * agent (ORB_SLAM2.1/Examples/ROS/ORB_SLAM2/src/ros_mono.cc:1907-2410) and decoded into

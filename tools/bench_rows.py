@@ -18,6 +18,10 @@
                (H2D + whole pipeline + D2H): the Tracking thread's per-frame latency, vs the oracle.
   matcher_host SearchForTriangulation (BF and over BoW nodes), SearchByBoW(KF,F), SearchByBoW(KF,KF)
                through the host C ABI, one keyframe pair per call (how the C++ drop-ins call them).
+  kfdb         KeyFrameDatabase query (orbdb_query_device): 4096 keyframes' BowVectors from the device BoW
+               transform of synthetic 640x480 frames (ORBvoc.txt-shaped synthetic vocabulary) resident in HBM,
+               Q = 1 and Q = 8 queries taken in place from a transform batch; kernel time from HIP events and
+               the entry bytes read (sum of counts x 12 B per query) over it as a share of the HBM peak.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -358,6 +362,71 @@ def bench_bow(torch, reps):
     # (pipe's buffers are torch tensors; its handles close with the process)
 
 
+def bench_kfdb(torch, reps):
+    import orbamd
+    from orbamd.database import KeyFrameDatabase
+    from orbamd.vocabulary import synth_vocabulary_full, L1_NORM, TF_IDF
+    HBM_PEAK = 8.0e12  # B/s, the MI355X's HBM3E specification
+    k, L, parent, leaf, desc, weight = synth_vocabulary_full(10, 6, 7)
+    gv = orbamd.ORBVocabulary.from_arrays(k, L, L1_NORM, TF_IDF, parent, leaf, desc, weight)
+    B, NB = 256, 16
+    pipe = orbamd.device.BatchPipeline(torch, 640, 480, B)
+    S, st = pipe.stride, pipe.stream_ptr()
+    db = KeyFrameDatabase(NB * B, min(S, 4096))
+    words = 0
+    for b in range(NB):  # 16 batches of 256 frames, each agent's own texture
+        pipe.extract(torch.from_numpy(orbamd.synth_frames(b, 0, B, 640, 480)).cuda())
+        pipe.bow(gv, 4)
+        for f in range(B):
+            db.add_device(b * B + f, pipe.bow_word[f], pipe.bow_val[f], pipe.nbow[f:f + 1], st)
+        words += int(pipe.nbow.sum().item())
+    assert not db.check_error(st) and len(db) == NB * B
+    dev = pipe.dev
+    lib = orbamd.load()
+    out = {}
+    for Q in (1, 8):
+        nc = torch.empty((Q, db.capacity), dtype=torch.int32, device=dev)
+        sc = torch.empty((Q, db.capacity), dtype=torch.float32, device=dev)
+        fw = torch.empty((Q, db.capacity), dtype=torch.int32, device=dev)
+
+        def run():
+            # the queries: rows 0 .. Q-1 of the last transform batch, in place
+            rc = lib.orbdb_query_device(db._h, Q, pipe.bow_word.data_ptr(), 4 * S, pipe.bow_val.data_ptr(), 8 * S,
+                                        pipe.nbow.data_ptr(), 4, nc.data_ptr(), sc.data_ptr(), fw.data_ptr(), st)
+            assert rc == 0
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of `reps` queries: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / reps)
+        # query q is keyframe (NB-1)*B + q itself: every word common, score 1 up to rounding
+        keys, slots = db.entries()
+        own = slots[(NB - 1) * B:(NB - 1) * B + Q]
+        q_i = torch.arange(Q, device=dev)
+        own_t = torch.from_numpy(own.astype(np.int64)).to(dev)
+        assert torch.equal(nc[q_i, own_t], pipe.nbow[:Q]) and bool(((sc[q_i, own_t] - 1).abs() < 1e-6).all())
+        t = float(np.median(times))
+        out[Q] = (t, min(times), max(times), 12.0 * words * Q / (t * 1e-3))
+    row = {"row": "kfdb_query", "workload": "%d keyframes x %.0f words (12 B each), vocabulary k=10 L=6, queries of "
+           "~%.0f words in place from a transform batch" % (NB * B, words / (NB * B), words / (NB * B)),
+           "entry_bytes_per_query": 12 * words}
+    for Q, (t, lo, hi, rate) in out.items():
+        row["q%d_ms_per_launch" % Q] = round(t, 4)
+        row["q%d_ms_min_max" % Q] = [round(lo, 4), round(hi, 4)]
+        row["q%d_entry_bytes_per_s" % Q] = round(rate, 0)
+        row["q%d_share_of_hbm_peak_8TBps" % Q] = round(rate / HBM_PEAK, 4)
+    db.close()
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -365,7 +434,7 @@ def main():
     rows = {"extract_host": lambda: bench_extract_host(100), "matcher_host": lambda: bench_matcher_host(100),
             "stereo": lambda: bench_stereo(torch, steps), "projection": lambda: bench_projection(50), "fuse": lambda: bench_fuse(50),
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
-            "tri_nodes": lambda: bench_tri_nodes(torch, 10)}
+            "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
