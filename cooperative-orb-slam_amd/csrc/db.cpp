@@ -3,35 +3,16 @@
  * free list and the insertion sequence numbers of KeyFrameDatabase's inverted file (KeyFrameDatabase.cc:40-73),
  * and the sequencing of db_kernels.hip on the caller's stream. The candidate selection is db_select.c.
  */
-#include <hip/hip_runtime.h>
-
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <map>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
 
-#include "../../include/orbslam_amd.h"
+#include "host_util.h"
+#include "launch.h"
 #include "orb_db.h"
 
 using namespace orbamd;
-
-#define HIPR(expr)                                                                    \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess) {                                                       \
-            if (getenv("ORBX_DEBUG")) fprintf(stderr, "HIP error %s at %s:%d\n",     \
-                                              hipGetErrorString(e_), __FILE__, __LINE__); \
-            (void)hipGetLastError();                                                  \
-            return ORBX_EDEVICE;                                                      \
-        }                                                                             \
-    } while (0)
-
-namespace orbamd {
-hipError_t launch_flag_take(int32_t* flag, int32_t* out, hipStream_t st);
-}
 
 struct orbdb_handle {
     int device = 0, capacity = 0, stride = 0;
@@ -57,8 +38,6 @@ struct orbdb_handle {
 
 namespace {
 
-size_t align256(size_t v) { return (v + 255) / 256 * 256; }
-
 /* device storage at first use (orbdb_create needs no device); the caller holds db->mu */
 int ensure_storage(orbdb_handle* db) {
     if (db->storage) return 0;
@@ -66,17 +45,17 @@ int ensure_storage(orbdb_handle* db) {
     HIPR(hipSetDevice(db->device));
     const size_t C = (size_t)db->capacity, S = (size_t)db->stride;
     size_t off = 0;
-    const size_t o_val = off; off += align256(8 * C * S);
-    const size_t o_word = off; off += align256(4 * C * S);
-    const size_t o_cnt = off; off += align256(4 * C);
-    const size_t o_live = off; off += align256(4 * C);
+    const size_t o_val = off; off += align_up(8 * C * S, 256);
+    const size_t o_word = off; off += align_up(4 * C * S, 256);
+    const size_t o_cnt = off; off += align_up(4 * C, 256);
+    const size_t o_live = off; off += align_up(4 * C, 256);
     const size_t o_err = off; off += 256;
-    const size_t o_qv = off; off += align256(8 * (size_t)kDbMaxWords);
-    const size_t o_qw = off; off += align256(4 * (size_t)kDbMaxWords);
+    const size_t o_qv = off; off += align_up(8 * (size_t)kDbMaxWords, 256);
+    const size_t o_qw = off; off += align_up(4 * (size_t)kDbMaxWords, 256);
     const size_t o_qc = off; off += 256;
-    const size_t o_rn = off; off += align256(4 * C);
-    const size_t o_rs = off; off += align256(4 * C);
-    const size_t o_rf = off; off += align256(4 * C);
+    const size_t o_rn = off; off += align_up(4 * C, 256);
+    const size_t o_rs = off; off += align_up(4 * C, 256);
+    const size_t o_rf = off; off += align_up(4 * C, 256);
     void* p = nullptr;
     HIPR(hipMalloc(&p, off));
     uint8_t* b = (uint8_t*)p;

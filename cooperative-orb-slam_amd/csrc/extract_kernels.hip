@@ -10,7 +10,7 @@
  *                    output assembly, 16 lanes per keypoint (ORBextractor.cc:77-147, 851-852, 1075-1104)
  *   k_blur_strips +  the same as two stages (whole-level blur, then describe) for frames whose level-0 rows
  *   k_describe       are not 4-aligned
- * capi.cpp runs them in order on the caller's stream (the separate blur on a side stream beside FAST and the
+ * extract.cpp runs them in order on the caller's stream (the separate blur on a side stream beside FAST and the
  * octree; DESIGN.md "Schedule").
  * All of it is integer/byte work bounded by HBM/LDS and VALU issue; no MFMA.
  * Exact-semantics notes live in DESIGN.md "Pinned semantics".
@@ -2136,7 +2136,7 @@ __global__ void k_sincos_selftest(const float* __restrict__ in, float* __restric
 }  // namespace orbamd
 
 /* ----------------------------------------------------------------------------------- */
-/* host-side launchers (called from capi.cpp)                                           */
+/* host-side launchers (called from extract.cpp)                                        */
 /* ----------------------------------------------------------------------------------- */
 #include "launch.h"
 

@@ -318,7 +318,7 @@ __device__ void call_tail(const CallTail& t) {
     if (threadIdx.x == 0) {
         t.state[1] = 0;
         t.state[0] = 0;
-        // the count is the call's completion word: the host polls it (capi.cpp wait_call) instead of
+        // the count is the call's completion word: the host polls it (matcher.cpp wait_call) instead of
         // synchronising the stream, so it is stored last, with release at system scope
         __hip_atomic_store(t.host_out, s_cnt, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
@@ -596,7 +596,7 @@ __device__ __forceinline__ void small_emit(unsigned long long* slot, int x, int 
 /* Small per-call SearchByBoW (BowSmall, orb_match.h): k_bow's lane-per-candidate greedy chain for nodes of
  * <= 64 candidates with every input in node order, no global atomics and no last-workgroup tail: a
  * workgroup emits its node's accepts (with their rotation bin) straight to host memory, then its done word
- * (the host waits for both). The rotation histogram over all nodes (ORBmatcher.cc:236-246, 1601-1642) is the host's (capi.cpp). */
+ * (the host waits for both). The rotation histogram over all nodes (ORBmatcher.cc:236-246, 1601-1642) is the host's (matcher.cpp). */
 __global__ __launch_bounds__(64) void k_bow_small(const BowSmall a) {
     const SmallTask t = a.tasks[blockIdx.x];
     const int lane = threadIdx.x;

@@ -1,5 +1,5 @@
 /*
- * orb_bow.h -- device view of a DBoW2 vocabulary (bow_kernels.hip, capi.cpp).
+ * orb_bow.h -- device view of a DBoW2 vocabulary (bow_kernels.hip, vocabulary.cpp).
  */
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 /*
- * orb_device.h -- geometry tables shared by the host launcher (capi.cpp) and the gfx950
+ * orb_device.h -- geometry tables shared by the host launcher (extract.cpp) and the gfx950
  * kernels. Everything that depends only on (W, H, ORB params) -- pyramid sizes, resize
  * coefficients, the FAST cell grid, octree root split -- is computed ONCE on the host with
  * the reference's exact float semantics and uploaded; kernels do integer work on it.

@@ -1,5 +1,5 @@
 /*
- * orb_match.h -- matcher argument structs shared by capi.cpp and match_kernels.hip, and ComputeThreeMaxima for
+ * orb_match.h -- matcher argument structs shared by matcher.cpp and match_kernels.hip, and ComputeThreeMaxima for
  * both sides. The matcher's device-side rules are in orb_match_dev.h.
  */
 #pragma once

@@ -1,6 +1,6 @@
 /*
  * orb_slot.h -- layout of the cross-agent keyframe slot (include/orbslam_amd.h, "Cross-agent
- * keyframe slot"), shared by the host C ABI (capi.cpp) and the device pack / match kernels
+ * keyframe slot"), shared by the host C ABI (slots.cpp) and the device pack / match kernels
  * (exchange_kernels.hip) so both compute the same section offsets from the capacity.
  */
 #pragma once

@@ -20,8 +20,8 @@ RING = [(0, 3), (1, 3), (2, 2), (3, 1), (3, 0), (3, -1), (2, -2), (1, -3), (0, -
         (-3, 0), (-3, 1), (-2, 2), (-1, 3)]
 W0, H0 = 120, 100
 FAST_PARAMS = [(20, 7), (21, 8), (7, 7), (7, 20), (1, 0), (255, 254)]
-# Geometry::build's LDS key limit at 256 octree nodes (capi.cpp key_lds, restated in key_limit below). The product has
-# no getter for it: key_limit and the constants of resize_fits must move together with capi.cpp / orb_device.h, or
+# Geometry::build's LDS key limit at 256 octree nodes (extract.cpp key_lds, restated in key_limit below). The product has
+# no getter for it: key_limit and the constants of resize_fits must move together with extract.cpp / orb_device.h, or
 # octree/global_scratch and the pyramid/scale_* cases stop reaching the instantiations their names claim.
 KL_256 = 1888
 

@@ -171,7 +171,7 @@ def test_small_bow_and_projection_alternate_on_one_context():
 
 def test_library_hip_failure_does_not_leak():
     """A HIP runtime call that fails inside liborbamd is reported through the entry point's status and cleared from
-    the calling thread's HIP error state (capi.cpp HIPR). Round 5's first GPU run raised a library-internal
+    the calling thread's HIP error state (host_util.h HIPR). Round 5's first GPU run raised a library-internal
     hipEventElapsedTime failure (an unrecorded stage event pair in orbx_profile_read, whose status bench.py ignored)
     as "HIP error: invalid resource handle" inside torch's next launch check (dist.barrier); with the failure left in
     the thread's error state the torch launch below raises the same way."""

@@ -35,7 +35,7 @@ def host():
 
 
 def _tri_kernel(c):
-    """capi.cpp tri_common: `max_nc <= 256 && tasks.size() <= (size_t)kSmallTasks && kf1->n <= 65535 && kf2->n <=
+    """matcher.cpp tri_common: `max_nc <= 256 && tasks.size() <= (size_t)kSmallTasks && kf1->n <= 65535 && kf2->n <=
     65535 && node_feats(kf1) <= 32 * kSmallBitWords && node_feats(kf2) <= 32 * kSmallBitWords` -> k_tri_small,
     else k_tri_nodes (kSmallTasks = 160, 32 * kSmallBitWords = 2048; a task = 64 queries of a common node)"""
     v1, v2 = c.views()
@@ -53,7 +53,7 @@ def _tri_kernel(c):
 
 
 def _bow_kernel(c):
-    """capi.cpp bow_common: `max_nc <= 64 && ... tasks.size() <= (size_t)kSmallTasks && node_feats(vq) <= 32 *
+    """matcher.cpp bow_common: `max_nc <= 64 && ... tasks.size() <= (size_t)kSmallTasks && node_feats(vq) <= 32 *
     kSmallBitWords && node_feats(vc) <= 32 * kSmallBitWords` -> k_bow_small; else launch_bow: `max_nc <= kBowStage`
     (512) -> k_bow<true>, whose nodes of `nc <= 64` take the lane-per-candidate branch and the others the staged
     one; else k_bow<false>"""

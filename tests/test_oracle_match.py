@@ -180,7 +180,7 @@ def test_match_cases_mfma_structure():
 
 
 def _dispatch(c):
-    """what capi.cpp's tri_common looks at: the largest candidate node among the common nodes, the number of
+    """what matcher.cpp's tri_common looks at: the largest candidate node among the common nodes, the number of
     64-query tasks, and the FeatureVector entries of each side"""
     v1, v2 = c.views()
     ids2 = {int(n): k for k, n in enumerate(v2.node_id)}
