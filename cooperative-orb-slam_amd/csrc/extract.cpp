@@ -798,7 +798,9 @@ static int extract_graph(orbx_handle* h, const uint8_t* img, int width, int heig
                          uint8_t* desc, int cap, int* n) {
     const int K = h->geo.ep.kp_per_frame;
     const size_t in_bytes = (size_t)width * height;
-    const size_t out_bytes = 64 + (sizeof(orbx_kp) + 32) * (size_t)K;
+    const bool un = h->cam_on;  // orbx_set_camera: one more node, mvKeysUn behind the descriptors
+    const size_t un_off = 64 + (sizeof(orbx_kp) + 32) * (size_t)K;
+    const size_t out_bytes = un_off + (un ? sizeof(orbx_kp) * (size_t)K : 0);
     if (h->pin_in_bytes < in_bytes) {
         if (h->pin_in) (void)hipHostFree(h->pin_in);
         h->pin_in = nullptr;
@@ -850,10 +852,17 @@ static int extract_graph(orbx_handle* h, const uint8_t* img, int width, int heig
     uint8_t* d_out = h->pin_out_dev;
     auto enqueue = [&]() -> int {
         HIPR(hipMemcpyAsync(h->in_frame.p, h->pin_in, in_bytes, hipMemcpyHostToDevice, h->stream));
-        int rc = run_extract(h, 1, h->in_frame.as<uint8_t>(), (long long)in_bytes, width, (orbx_kp*)(d_out + 64),
-                             d_out + 64 + sizeof(orbx_kp) * (size_t)K, (int32_t*)d_out, K, h->stream, true, true,
-                             copies ? &hc : nullptr);
+        // with a camera describe leaves keypoints and count in HBM and the undistort node delivers them, raw and
+        // undistorted, so no kernel reads across PCIe
+        int rc = run_extract(h, 1, h->in_frame.as<uint8_t>(), (long long)in_bytes, width,
+                             un ? h->out_kps.as<orbx_kp>() : (orbx_kp*)(d_out + 64),
+                             d_out + 64 + sizeof(orbx_kp) * (size_t)K, un ? h->out_cnt.as<int32_t>() : (int32_t*)d_out,
+                             K, h->stream, true, true, copies ? &hc : nullptr);
         if (rc) return rc;
+        if (un)
+            HIPR(launch_undistort_deliver(h->cam, h->out_kps.as<orbx_kp>(), h->out_cnt.as<int32_t>(), K,
+                                          (orbx_kp*)(d_out + 64), (orbx_kp*)(d_out + un_off), (int32_t*)d_out,
+                                          h->stream));
         HIPR(launch_call_done(h->err.as<int32_t>() + kErrWordExtract, (int32_t*)(d_out + 4),
                               h->err.as<int32_t>() + kErrWordExtractSeq, (int32_t*)(d_out + 8), h->stream));
         return 0;
@@ -910,6 +919,9 @@ static int extract_graph(orbx_handle* h, const uint8_t* img, int width, int heig
         if (desc) memcpy(desc, o_desc, 32 * (size_t)cnt);
     }
     *n = cnt;
+    h->un_valid = un && !(h->skip_mask & 16) && cnt <= K;
+    h->un_count = cnt;
+    h->un_off = un_off;
     return 0;
 }
 
@@ -921,6 +933,7 @@ int orbx_extract(orbx_handle* h, const uint8_t* img, int width, int height, size
     if (pitch < (size_t)width) return ORBX_EARG;
     HIPR(hipSetDevice(h->device));
     h->host_pyr_valid = false;
+    h->un_valid = false;
     if (ensure_stream(h, &h->stream)) return ORBX_EDEVICE;
     int rc = ensure_geometry(h, width, height, 1);
     if (rc) return rc;
@@ -953,6 +966,27 @@ int orbx_extract(orbx_handle* h, const uint8_t* img, int width, int height, size
         HIPR(hipStreamSynchronize(h->stream));
     }
     *n = cnt;
+    return 0;
+}
+
+int orbx_set_camera(orbx_handle* h, const orbx_camera* cam) {
+    if (!h || (cam && (cam->fx == 0 || cam->fy == 0))) return ORBX_EARG;
+    h->cam_on = cam != nullptr;
+    if (cam) h->cam = *cam;
+    h->un_valid = false;
+    h->epoch++;  // the captured host-call graph holds the camera and whether it undistorts
+    return 0;
+}
+
+int orbx_last_keypoints_un(orbx_handle* h, orbx_kp* kps_un, int cap, int* n) {
+    if (!h || !n || cap < 0 || !h->un_valid) return ORBX_EARG;
+    *n = 0;
+    if (h->un_count > cap) return ORBX_ECAPACITY;
+    if (h->un_count > 0) {
+        if (!kps_un) return ORBX_EARG;
+        memcpy(kps_un, h->pin_out + h->un_off, sizeof(orbx_kp) * (size_t)h->un_count);
+    }
+    *n = h->un_count;
     return 0;
 }
 

@@ -133,6 +133,13 @@ struct orbx_handle {
     uint8_t* target_dev = nullptr;
     size_t target_bytes = 0;
     uint8_t* last_target = nullptr;
+    // orbx_set_camera: the host call's graph also undistorts (k_undistort<true>) and delivers mvKeysUn behind the
+    // descriptors of pin_out; un_valid / un_count / un_off describe what the last orbx_extract delivered
+    bool cam_on = false;
+    orbx_camera cam{};
+    bool un_valid = false;
+    int un_count = 0;
+    size_t un_off = 0;
     // stage profiling (orbx_profile_*)
     bool prof_on = false;
     int prof_mask = 0;  // stages with event pairs (bit k = stage k)

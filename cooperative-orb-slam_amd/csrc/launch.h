@@ -79,6 +79,13 @@ hipError_t launch_tri_small(const TriSmall& a, hipStream_t st);
 hipError_t launch_rot_filter(int n, int32_t* m, const float* angA, const float* angB, int swap, int32_t* nout,
                              hipStream_t st);
 
+/* Frame::UndistortKeyPoints of every frame of a batch (kun: optional x, y pairs; kps_un may equal kps) */
+hipError_t launch_undistort(const orbx_camera& cam, int nframes, const orbx_kp* kps, const int32_t* counts,
+                            int kp_stride, orbx_kp* kps_un, float* kun, hipStream_t st);
+/* the one-frame host call with a camera: device keypoints / count -> the call's pinned buffer, raw and undistorted */
+hipError_t launch_undistort_deliver(const orbx_camera& cam, const orbx_kp* kps, const int32_t* count, int kp_stride,
+                                    orbx_kp* raw_out, orbx_kp* un_out, int32_t* count_out, hipStream_t st);
+
 hipError_t launch_flag_take(int32_t* flag, int32_t* out, hipStream_t st);
 hipError_t launch_call_done(int32_t* flag, int32_t* out_err, int32_t* seq, int32_t* out_done, hipStream_t st);
 hipError_t launch_pack_slot(const orbx_kf_source& src, const SlotLayout& L, const orbx_kf_meta& meta, uint8_t* slot,

@@ -9,6 +9,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "Frame_undistort_amd.h"
 #include "orbamd_status.h"
 #include "orbslam_amd.h"
 
@@ -154,7 +155,15 @@ int ORBextractor::ensureHandle(int width, int height) {
     // eager mvImagePyramid: every call also delivers the levels into the handle's pinned memory (copied beside the
     // octree on the device), so SyncImagePyramid only points the member's Mats at them
     if (HostPyramidEager()) amd::StatusOk(orbx_set_host_pyramid(h, 1), "orbx_set_host_pyramid");
+    if (mbCamera) amd::StatusOk(orbx_set_camera(h, &mCamera), "orbx_set_camera");
     return ORBX_OK;
+}
+
+void ORBextractor::SetCamera(const cv::Mat& K, const cv::Mat& distCoef) {
+    mCamera = amd::MakeCamera(K, distCoef);
+    mbCamera = true;
+    // a handle created later (the first frame, or after a device failure) gets the camera in ensureHandle
+    if (mpHandle) amd::StatusOk(orbx_set_camera(mpHandle, &mCamera), "orbx_set_camera");
 }
 
 void ORBextractor::failed(int rc, const char* what, std::vector<cv::KeyPoint>& kps, cv::OutputArray desc) {

@@ -70,6 +70,13 @@ public:
     // whether operator() fills mvImagePyramid itself (see above); addition
     bool HostPyramidEager() const;
 
+    // mK / mDistCoef of the Frames this extractor serves (Tracking.cc:54-77); addition. With a camera set every
+    // operator() also undistorts its keypoints on the device (orbx_set_camera), and amd::UndistortKeyPoints
+    // (host/Frame_undistort_amd.h) takes mvKeysUn from that call instead of computing it on the host.
+    void SetCamera(const cv::Mat& K, const cv::Mat& distCoef);
+    bool HasCamera() const { return mbCamera; }
+    const orbx_camera& Camera() const { return mCamera; }
+
 protected:
     int ensureHandle(int width, int height);
     orbx_params params() const;
@@ -91,6 +98,8 @@ protected:
     int mHostPyramid;     // ORBAMD_HOST_PYRAMID: 1 eager, 0 lazy, -1 (unset) eager unless a device reader is linked
     bool mbPyramidStale;  // mvImagePyramid does not hold the last call's levels yet
     int mLastStatus = 0;
+    bool mbCamera = false;
+    orbx_camera mCamera = {};
     std::vector<unsigned char> mKpBuf, mDescBuf;
     // eager mvImagePyramid storage: refcounted buffers registered for device writes (orbx_host_register); a call
     // fills one no caller holds (selectPyramidSlot), the member's Mats are views sharing its reference count

@@ -29,6 +29,11 @@ class OrbxKp(C.Structure):
                 ("response", C.c_float), ("octave", C.c_int32)]
 
 
+class OrbxCamera(C.Structure):
+    """orbx_camera: the float members of mK and mDistCoef (k3 = 0 for a 4-entry mDistCoef)."""
+    _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
+
+
 class OrbmKfView(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
                 ("angle", C.c_void_p), ("octave", C.c_void_p), ("uright", C.c_void_p),
@@ -154,6 +159,12 @@ SIGNATURES = {
     "orbx_stereo_matches_batch_device": (_I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _F, _F, _P, _P, _P,
                                               _P]),
     "orbx_check_error": (_I, [_P, _P]),
+    "orbx_undistort_points": (_I, [C.POINTER(OrbxCamera), _I, _P, _P]),
+    "orbx_undistort_keypoints": (_I, [C.POINTER(OrbxCamera), _I, _P, _P]),
+    "orbx_image_bounds": (_I, [C.POINTER(OrbxCamera), _I, _I, _P, C.POINTER(_F), C.POINTER(_F)]),
+    "orbx_set_camera": (_I, [_P, C.POINTER(OrbxCamera)]),
+    "orbx_last_keypoints_un": (_I, [_P, _P, _I, C.POINTER(_I)]),
+    "orbx_undistort_batch_device": (_I, [_P, C.POINTER(OrbxCamera), _I, _P, _P, _I, _P, _P, _P]),
     "orbm_search_by_projection_local": (_I, [_P, _P, _P, _F, _F, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_last_frame": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_keyframe": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),

@@ -52,11 +52,13 @@ def kf_mp_flags(n):
 class AgentSchedule:
     def __init__(self, torch, frames_np, width, height, pipes, device=0, rank=0, world=1, allgather=None,
                  stagger=DEFAULT_STAGGER, exchange=True, priorities=None, nfeatures=1000, pool=1,
-                 async_exchange=False, stereo=None):
+                 async_exchange=False, stereo=None, camera=None):
         """frames_np: uint8 [pool*B, H, W] host frames of this agent (copied to HBM once), batch r = frames
         [r*B, (r+1)*B); with stereo=(mbf, mb) uint8 [pool*B, 2, H, W] (left, right image of each frame);
         allgather(out, inp): all-gather of equal-sized device byte tensors across agents (None: no collective,
-        only possible at world 1, where the slot is packed in place)."""
+        only possible at world 1, where the slot is packed in place); camera: a distorted camera
+        (BatchPipeline): every graph undistorts its keypoints after extracting them, the matchers read mvKeysUn and
+        the keyframe slot carries it (KUN)."""
         assert len(frames_np) % pool == 0
         assert (frames_np.ndim == 4 and frames_np.shape[1] == 2) == bool(stereo), "stereo frames are [N, 2, H, W]"
         self.stereo = stereo
@@ -97,7 +99,8 @@ class AgentSchedule:
                 row.append(view)
             self.frames.append(row)
         self.nfeatures = nfeatures
-        self.pipes = [BatchPipeline(torch, width, height, sub, nfeatures=nfeatures, device=device, stereo=stereo)
+        self.pipes = [BatchPipeline(torch, width, height, sub, nfeatures=nfeatures, device=device, stereo=stereo,
+                                    camera=camera)
                       for _ in range(pipes)]
         prio = priorities or [0] * pipes
         self.streams = [torch.cuda.Stream(dev, priority=prio[p]) for p in range(pipes)]
@@ -134,12 +137,16 @@ class AgentSchedule:
         # own stream when a collective runs, graph 0's at N = 1, where it measured 0.9 % faster).
         self.xstream = None
         kps, desc, count = p0.kps[0], p0.desc[0], p0.counts[0:1]
+        kun = p0.kun[0] if p0.kun is not None else None
         if async_exchange and exchange:
             self.xstream = torch.cuda.Stream(dev)
             self.q_kps = torch.empty_like(p0.kps[0])
             self.q_desc = torch.empty_like(p0.desc[0])
             self.q_count = torch.empty_like(p0.counts[0:1])
             kps, desc, count = self.q_kps, self.q_desc, self.q_count
+            if kun is not None:
+                self.q_kun = torch.empty_like(p0.kun[0])
+                kun = self.q_kun
             self.kf_released = torch.cuda.Event()
             self.kf_pending = False
         self.kf_stereo = (None, None)
@@ -165,7 +172,7 @@ class AgentSchedule:
             self.kf_fv_node, self.kf_fv_off, self.kf_fv_feat, self.kf_nfv = z(S), z(S + 1), z(S), z(1)
             self.kf_mpf = torch.from_numpy(kf_mp_flags(S)).to(dev)
             self.bow_max_nodes = int(min(S, k ** max(L - KF_LEVELSUP, 0)))
-            self.kf_src = kf_source(kps, desc, count, uright=self.kf_stereo[0], depth=self.kf_stereo[1],
+            self.kf_src = kf_source(kps, desc, count, kun=kun, uright=self.kf_stereo[0], depth=self.kf_stereo[1],
                                     mp_flags=self.kf_mpf, bow_word=self.kf_bow_word,
                                     bow_value=self.kf_bow_val, nbow=self.kf_nbow, fv_node=self.kf_fv_node,
                                     fv_off=self.kf_fv_off, fv_feat=self.kf_fv_feat, nfv=self.kf_nfv)
@@ -213,6 +220,8 @@ class AgentSchedule:
                 kps.copy_(p0.kps[0])
                 desc.copy_(p0.desc[0])
                 count.copy_(p0.counts[0:1])
+                if p0.kun is not None:
+                    self.q_kun.copy_(p0.kun[0])
                 if self.stereo:
                     self.q_uright.copy_(p0.uright[0])
                     self.q_depth.copy_(p0.depth[0])
@@ -308,6 +317,10 @@ class AgentSchedule:
         """(keypoints, descriptors, match12 vs frame b-1 of the same graph) of frame b of graph p (stereo: its left
         image)"""
         return self.pipes[p].host_results(b)
+
+    def host_keypoints_un(self, p, b):
+        """mvKeysUn of frame b of graph p (stereo: its left image)"""
+        return self.pipes[p].host_keypoints_un(b)
 
     def stereo_results(self, p, b):
         """stereo: ((right keypoints, right descriptors), (mvuRight, mvDepth, kept)) of frame b of graph p"""

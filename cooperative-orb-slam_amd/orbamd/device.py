@@ -45,10 +45,15 @@ class BatchPipeline:
     one orbx_extract_batch_device over all 2B (the two ORBextractor instances share the parameters,
     Tracking.cc:119-125); Frame::ComputeStereoMatches gives every left keypoint its mvuRight / mvDepth
     (orbx_stereo_matches_batch_device), and SearchForTriangulation of frame b against b-1 takes the stereo branch
-    (orbm_triangulation_bf_stereo_batch_device)."""
+    (orbm_triangulation_bf_stereo_batch_device).
+
+    camera=(fx, fy, cx, cy, k1, k2, p1, p2[, k3]) (orbamd.frame.make_camera): a distorted camera. Every extraction is
+    followed on the same stream by Frame::UndistortKeyPoints on the device (orbx_undistort_batch_device) into kps_un
+    (mvKeysUn, what every matcher here reads) and kun (their x, y: the keyframe slot's KUN section); kps stays
+    mvKeys. camera=None: mvKeysUn = mvKeys, no launch, no extra buffer."""
 
     def __init__(self, torch, width=640, height=480, batch=64, nfeatures=1000, scale=1.2, nlevels=8, ini=20, mini=7,
-                 device=0, check_ori=False, stereo=None):
+                 device=0, check_ori=False, stereo=None, camera=None):
         self.torch = torch
         self.W, self.H, self.B = width, height, batch
         self.stereo = stereo
@@ -63,6 +68,13 @@ class BatchPipeline:
         self.kps = torch.empty((nimg, self.stride, 6), dtype=torch.float32, device=dev)
         self.desc = torch.empty((nimg, self.stride, 32), dtype=torch.uint8, device=dev)
         self.counts = torch.zeros(nimg, dtype=torch.int32, device=dev)
+        self.camera = None
+        self.kps_un, self.kun = self.kps, None  # mvKeysUn = mvKeys without a camera
+        if camera is not None:
+            from .frame import make_camera
+            self.camera = make_camera(camera)
+            self.kps_un = torch.empty_like(self.kps)
+            self.kun = torch.empty((nimg, self.stride, 2), dtype=torch.float32, device=dev)
         self.match = torch.empty((batch, self.stride), dtype=torch.int32, device=dev)
         self.nmatch = torch.zeros(batch, dtype=torch.int32, device=dev)
         self.q1 = torch.arange(batch, dtype=torch.int32, device=dev)
@@ -88,6 +100,8 @@ class BatchPipeline:
         then runs ComputeStereoMatches for every pair on the same stream (stereo=False: the caller does)"""
         st = self.stream_ptr() if stream is None else stream
         self.ext.extract_batch_device(frames, self.kps, self.desc, self.counts, st)
+        if self.camera is not None:
+            self.ext.undistort_batch_device(self.camera, self.kps, self.counts, self.kps_un, self.kun, st)
         if self.stereo and stereo:
             self.stereo_matches(st)
 
@@ -110,13 +124,13 @@ class BatchPipeline:
         F = np.ascontiguousarray(self.F12.reshape(9))
         if self.stereo:
             check(self.lib.orbm_triangulation_bf_stereo_batch_device(
-                self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps.data_ptr(), self.desc.data_ptr(),
+                self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps_un.data_ptr(), self.desc.data_ptr(),
                 self.counts.data_ptr(), self.uright.data_ptr(), self.stride, F.ctypes.data, self.ex, self.ey,
                 len(self.scale), self.scale.ctypes.data, self.sigma2.ctypes.data, 0, self.check_ori,
                 self.match.data_ptr(), self.nmatch.data_ptr(), st), "orbm_triangulation_bf_stereo_batch_device")
             return
         check(self.lib.orbm_triangulation_bf_batch_device(
-            self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps.data_ptr(), self.desc.data_ptr(),
+            self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps_un.data_ptr(), self.desc.data_ptr(),
             self.counts.data_ptr(), self.stride, F.ctypes.data, self.ex, self.ey, len(self.scale),
             self.scale.ctypes.data, self.sigma2.ctypes.data, self.check_ori, self.match.data_ptr(),
             self.nmatch.data_ptr(), st), "orbm_triangulation_bf_batch_device")
@@ -145,7 +159,7 @@ class BatchPipeline:
         st = self.stream_ptr() if stream is None else stream
         F = np.ascontiguousarray(self.F12.reshape(9))
         check(self.lib.orbm_triangulation_nodes_batch_device(
-            self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps.data_ptr(), self.desc.data_ptr(),
+            self.mh, self.B, self.q1.data_ptr(), self.q2.data_ptr(), self.kps_un.data_ptr(), self.desc.data_ptr(),
             self.counts.data_ptr(), self.stride, self.fv_node.data_ptr(), self.fv_off.data_ptr(),
             self.fv_feat.data_ptr(), self.nfv.data_ptr(), self.max_nodes, F.ctypes.data, self.ex, self.ey,
             len(self.scale), self.scale.ctypes.data, self.sigma2.ctypes.data, self.check_ori, self.match.data_ptr(),
@@ -156,10 +170,10 @@ class BatchPipeline:
         cuda [npairs]; mp_flags uint8 cuda [B, stride] (bit 0 MapPoint, bit 1 bad); out int32 [npairs, stride]."""
         st = self.stream_ptr() if stream is None else stream
         check(self.lib.orbm_search_by_bow_batch_device(
-            self.mh, int(qf.numel()), int(mode), qf.data_ptr(), cf.data_ptr(), self.kps.data_ptr(), self.desc.data_ptr(),
-            self.counts.data_ptr(), self.stride, mp_flags.data_ptr(), self.fv_node.data_ptr(), self.fv_off.data_ptr(),
-            self.fv_feat.data_ptr(), self.nfv.data_ptr(), self.max_nodes, float(nnratio), int(check_ori),
-            out.data_ptr(), nmatches.data_ptr(), st), "orbm_search_by_bow_batch_device")
+            self.mh, int(qf.numel()), int(mode), qf.data_ptr(), cf.data_ptr(), self.kps_un.data_ptr(),
+            self.desc.data_ptr(), self.counts.data_ptr(), self.stride, mp_flags.data_ptr(), self.fv_node.data_ptr(),
+            self.fv_off.data_ptr(), self.fv_feat.data_ptr(), self.nfv.data_ptr(), self.max_nodes, float(nnratio),
+            int(check_ori), out.data_ptr(), nmatches.data_ptr(), st), "orbm_search_by_bow_batch_device")
 
     def step(self, frames, stream=None):
         self.extract(frames, stream)
@@ -189,7 +203,8 @@ class BatchPipeline:
         if with_bow:
             kw = dict(bow_word=self.bow_word[f], bow_value=self.bow_val[f], nbow=self.nbow[f:f + 1],
                       fv_node=self.fv_node[f], fv_off=self.fv_off[f], fv_feat=self.fv_feat[f], nfv=self.nfv[f:f + 1])
-        return kf_source(self.kps[f], self.desc[f], self.counts[f:f + 1], uright=uright, depth=depth,
+        kun = self.kun[f] if self.kun is not None else None  # a distorted camera: the slot carries mvKeysUn (KUN)
+        return kf_source(self.kps[f], self.desc[f], self.counts[f:f + 1], kun=kun, uright=uright, depth=depth,
                          mp_flags=mp_flags, mp_pos=mp_pos, **kw)
 
     def pack(self, frame_idx, slot, meta, stream=None, with_bow=False, err=None, src=None):
@@ -232,6 +247,12 @@ class BatchPipeline:
         k = self.kps[i, :n].cpu().numpy().copy().view(np.uint8).view(kp_dtype).reshape(n)
         d = self.desc[i, :n].cpu().numpy()
         return k, d
+
+    def host_keypoints_un(self, i):
+        """mvKeysUn of extraction image i (Frame::UndistortKeyPoints; equal to its keypoints without a camera)"""
+        from .extractor import kp_dtype
+        n = int(self.counts[i].item())
+        return self.kps_un[i, :n].cpu().numpy().copy().view(np.uint8).view(kp_dtype).reshape(n)
 
     def host_stereo(self, b):
         """(mvuRight float32 [n], mvDepth float32 [n], stereo matches kept) of stereo frame b"""

@@ -143,3 +143,32 @@ class ORBextractor:
         check(self._lib.orbx_extract_batch_device(self._h, B, frames.data_ptr(), frames.stride(0), W, H,
                                                   frames.stride(1), kps.data_ptr(), desc.data_ptr(),
                                                   counts.data_ptr(), stride, st), "orbx_extract_batch_device")
+
+    def undistort_batch_device(self, camera, kps, counts, kps_un, kun=None, stream=None):
+        """Frame::UndistortKeyPoints of every frame of an extract_batch_device output on the device
+        (orbx_undistort_batch_device): kps / kps_un cuda [B, stride, 6] (kps_un may be kps itself), counts int32
+        [B], kun optional float32 cuda [B, stride, 2] (the slot packer's `kun`). camera: see frame.make_camera."""
+        from .frame import make_camera
+        cam = make_camera(camera)
+        B, stride = kps.shape[0], kps.shape[1]
+        st = 0 if stream is None else stream
+        check(self._lib.orbx_undistort_batch_device(self._h, C.byref(cam), B, kps.data_ptr(), counts.data_ptr(),
+                                                    stride, kps_un.data_ptr(),
+                                                    None if kun is None else kun.data_ptr(), st),
+              "orbx_undistort_batch_device")
+
+    # ---- the one-frame path: mvKeysUn from the call's own graph
+    def set_camera(self, camera):
+        """orbx_set_camera: every later __call__ also undistorts its keypoints on the device (camera: see
+        frame.make_camera; None = off)."""
+        from .frame import make_camera
+        cam = None if camera is None else make_camera(camera)
+        check(self._lib.orbx_set_camera(self._h, None if cam is None else C.byref(cam)), "orbx_set_camera")
+
+    def last_keypoints_un(self):
+        """mvKeysUn of the last __call__ (orbx_last_keypoints_un); raises when that call delivered none."""
+        cap = self.max_keypoints(*self._last_shape) if self._last_shape else 0
+        kps = np.empty(cap, kp_dtype)
+        n = C.c_int(0)
+        check(self._lib.orbx_last_keypoints_un(self._h, kps.ctypes.data, cap, C.byref(n)), "orbx_last_keypoints_un")
+        return kps[:n.value].copy()

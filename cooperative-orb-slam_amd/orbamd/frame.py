@@ -3,12 +3,16 @@
 * :func:`compute_stereo_matches` -- ``Frame::ComputeStereoMatches``
   (ORB_SLAM2.1/src/Frame.cc:470-641): mvuRight / mvDepth of the left keypoints, from the two
   extractors' device-resident pyramids.
+* :func:`undistort_points`, :func:`undistort_keypoints`, :func:`image_bounds` --
+  ``Frame::UndistortKeyPoints`` (Frame.cc:405-435) and ``Frame::ComputeImageBounds`` (Frame.cc:437-465, with the
+  grid cell sizes of Frame.cc:213-214) on the host; the device batch form is
+  ``ORBextractor.undistort_batch_device``.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._lib import check, load
+from ._lib import KP_FIELDS, OrbxCamera, check, load
 
 
 def compute_stereo_matches(left, right, kpsL, descL, kpsR, descR, mbf, mb):
@@ -39,3 +43,53 @@ def stereo_matches_batch_device(left, right, fl, fr, kpsL, descL, cntL, kpsR, de
         left._h, right._h, fl.shape[0], fl.data_ptr(), fr.data_ptr(), kpsL.data_ptr(), descL.data_ptr(),
         cntL.data_ptr(), kpsR.data_ptr(), descR.data_ptr(), cntR.data_ptr(), stride, float(mbf), float(mb),
         uright.data_ptr(), depth.data_ptr(), nstereo.data_ptr(), stream), "orbx_stereo_matches_batch_device")
+
+
+def make_camera(camera):
+    """orbx_camera from an OrbxCamera, a mapping with the keys fx, fy, cx, cy, k1, k2, p1, p2[, k3] or a sequence
+    (fx, fy, cx, cy, k1, k2, p1, p2[, k3]); k3 = 0 for a 4-entry mDistCoef."""
+    if isinstance(camera, OrbxCamera):
+        return camera
+    names = [k for k, _ in OrbxCamera._fields_]
+    if hasattr(camera, "keys"):
+        vals = [float(camera[k]) if k in camera.keys() else 0.0 for k in names]
+        if not all(k in camera.keys() for k in names[:8]):
+            raise ValueError("camera needs fx, fy, cx, cy, k1, k2, p1, p2")
+    else:
+        vals = [float(v) for v in camera]
+        if len(vals) not in (8, 9):
+            raise ValueError("camera = (fx, fy, cx, cy, k1, k2, p1, p2[, k3])")
+        vals += [0.0] * (9 - len(vals))
+    return OrbxCamera(*vals)
+
+
+def undistort_points(camera, xy):
+    """The cv::undistortPoints call of Frame::UndistortKeyPoints (Frame.cc:423) with its k1 == 0 copy: xy float32
+    [n, 2] -> float32 [n, 2]."""
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    out = np.empty_like(xy)
+    cam = make_camera(camera)
+    check(load().orbx_undistort_points(C.byref(cam), len(xy), xy.ctypes.data, out.ctypes.data),
+          "orbx_undistort_points")
+    return out
+
+
+def undistort_keypoints(camera, kps):
+    """Frame::UndistortKeyPoints (Frame.cc:405-435): mvKeysUn of the keypoints (structured array of kp_dtype)."""
+    kps = np.ascontiguousarray(kps, np.dtype(KP_FIELDS))
+    out = np.empty_like(kps)
+    cam = make_camera(camera)
+    check(load().orbx_undistort_keypoints(C.byref(cam), len(kps), kps.ctypes.data, out.ctypes.data),
+          "orbx_undistort_keypoints")
+    return out
+
+
+def image_bounds(camera, cols, rows):
+    """Frame::ComputeImageBounds (Frame.cc:437-465) and Frame.cc:213-214: ((mnMinX, mnMaxX, mnMinY, mnMaxY) float32
+    [4], mfGridElementWidthInv, mfGridElementHeightInv as numpy float32)."""
+    b = np.empty(4, np.float32)
+    gw, gh = C.c_float(), C.c_float()
+    cam = make_camera(camera)
+    check(load().orbx_image_bounds(C.byref(cam), int(cols), int(rows), b.ctypes.data, C.byref(gw), C.byref(gh)),
+          "orbx_image_bounds")
+    return b, np.float32(gw.value), np.float32(gh.value)

@@ -250,6 +250,10 @@ int orbm_search_by_bow_batch_device(orbm_ctx* ctx, int npairs, int mode, const i
                                     int check_ori, int32_t* d_out, int32_t* d_nmatches,
                                     void* stream);
 
+/* The four batches above read d_kps as the keyframes' mvKeysUn (the epipolar test is written on
+ * it, ORBmatcher.cc:743-760): with a distorted camera d_kps is the d_kps_un output of
+ * orbx_undistort_batch_device, not the extractor's own array. */
+
 /* Waits for `stream` and reports (then clears) the ctx's device error flag, raised by the
  * *_device calls that validate device-resident input (orbm_search_for_triangulation_slots_device:
  * a malformed or foreign slot, a query count above its capacity): 0 = OK, ORBX_EDEVICE. */
@@ -776,6 +780,55 @@ int orbx_stereo_matches_batch_device(orbx_handle* left, orbx_handle* right, int 
                                      const uint8_t* d_descR, const int32_t* d_cntR, int kp_stride,
                                      float bf, float b, float* d_uright, float* d_depth,
                                      int32_t* d_nstereo, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Undistorted keypoints -- replaces Frame::UndistortKeyPoints (ORB_SLAM2/src/Frame.cc:405-435)
+ * and Frame::ComputeImageBounds (Frame.cc:437-465) with the grid cell sizes derived from the
+ * bounds (Frame.cc:213-214). cv::undistortPoints(src, dst, K, D, noArray(), K) of OpenCV 3.x is
+ * restated from its published algorithm (parity unpinned; DESIGN.md "Pinned semantics"): five
+ * fixed-point iterations in double, no convergence test, then the projection with P = mK, one
+ * rounding to float. The reference's quirk stays: mDistCoef.at<float>(0) == 0.0 (k1 alone)
+ * means mvKeysUn = mvKeys and bounds (0, cols, 0, rows), whatever k2, p1, p2, k3 are.
+ * ---------------------------------------------------------------------------------- */
+
+/* The float members of mK (fx, fy, cx, cy) and mDistCoef (k1, k2, p1, p2[, k3]) as Tracking reads
+ * them from the settings file (Tracking.cc:54-77); k3 = 0 for a 4-entry mDistCoef. */
+typedef struct orbx_camera {
+    float fx, fy, cx, cy, k1, k2, p1, p2, k3;
+} orbx_camera;
+
+/* The cv::undistortPoints call of Frame::UndistortKeyPoints (Frame.cc:423) over n points
+ * (xy_in / xy_out: n x 2 floats; in place allowed), with the k1 == 0 copy of Frame.cc:407-411.
+ * Host only, no device. ORBX_EARG on NULL arguments, n < 0 or fx == 0 || fy == 0 (here and in the
+ * two calls below). */
+int orbx_undistort_points(const orbx_camera* cam, int n, const float* xy_in, float* xy_out);
+/* Frame::UndistortKeyPoints (Frame.cc:405-435): out[i] = in[i] with only (x, y) replaced
+ * (Frame.cc:430-433); in place allowed. Host only. */
+int orbx_undistort_keypoints(const orbx_camera* cam, int n, const orbx_kp* in, orbx_kp* out);
+/* Frame::ComputeImageBounds (Frame.cc:437-465) of a cols x rows image: bounds = {mnMinX, mnMaxX,
+ * mnMinY, mnMaxY}; grid_w_inv / grid_h_inv (either may be NULL) = mfGridElementWidthInv /
+ * mfGridElementHeightInv = 64.0f / (mnMaxX - mnMinX), 48.0f / (mnMaxY - mnMinY) in float
+ * (Frame.cc:213-214). Host only. */
+int orbx_image_bounds(const orbx_camera* cam, int cols, int rows, float bounds[4], float* grid_w_inv,
+                      float* grid_h_inv);
+/* Frame::UndistortKeyPoints (Frame.cc:405-435) for every frame of an orbx_extract_batch_device
+ * output (d_kps / d_counts / kp_stride as produced there), on the device: d_kps_un (a full
+ * orbx_kp array of the same layout; may equal d_kps) receives mvKeysUn and, when d_kun is not
+ * NULL, d_kun[(f*kp_stride + i)*2 .. +2) its (x, y) alone (orbx_kf_source::kun of frame f at
+ * d_kun + f*kp_stride*2). Only rows i < min(d_counts[f], kp_stride) are read or written. The
+ * arrays must be 8-byte aligned (ORBX_EARG otherwise). Enqueued on `stream`; no host sync. */
+int orbx_undistort_batch_device(orbx_handle* h, const orbx_camera* cam, int nframes, const orbx_kp* d_kps,
+                                const int32_t* d_counts, int kp_stride, orbx_kp* d_kps_un, float* d_kun,
+                                void* stream);
+
+/* The one-frame path: with a camera set (cam = NULL: off, the default) every subsequent orbx_extract on
+ * `h` also delivers Frame::UndistortKeyPoints (Frame.cc:405-435) of its keypoints, from one more
+ * kernel node of its captured graph into the handle's pinned memory, and orbx_last_keypoints_un copies
+ * them out after the call (kps_un[cap]; *n = their number, the call's keypoint count). ORBX_EARG when
+ * the last orbx_extract had no camera, was stage-profiled (orbx_profile_enable) or delivered nothing
+ * (empty image, error); ORBX_ECAPACITY if cap is smaller. Without a camera orbx_extract is unchanged. */
+int orbx_set_camera(orbx_handle* h, const orbx_camera* cam);
+int orbx_last_keypoints_un(orbx_handle* h, orbx_kp* kps_un, int cap, int* n);
 
 /* ------------------------------------------------------------------------------------
  * Synthetic input: deterministic frame t of agent a, width x height,

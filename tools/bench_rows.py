@@ -22,6 +22,10 @@
                transform of synthetic 640x480 frames (ORBvoc.txt-shaped synthetic vocabulary) resident in HBM,
                Q = 1 and Q = 8 queries taken in place from a transform batch; kernel time from HIP events and
                the entry bytes read (sum of counts x 12 B per query) over it as a share of the HBM peak.
+  undistort    Frame::UndistortKeyPoints on the device (orbx_undistort_batch_device) over the keypoints of a
+               1024-frame C2 extraction (640x480, 1000 features, my.yaml's distorted camera), with and without the
+               `kun` output: kernel time from HIP events around 200 launches (median of five windows, min-max), and the
+               bytes moved (sum of counts x 48 B, + 8 B with kun) over it as a share of the HBM peak.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -427,6 +431,53 @@ def bench_kfdb(torch, reps):
     return row
 
 
+def bench_undistort(torch, reps):
+    import orbamd
+    HBM_PEAK = 8.0e12  # B/s, the MI355X's HBM3E specification
+    B = 1024
+    cam = (715.092024, 719.025258, 334.298489, 256.326097, 0.085908, -0.07019499, 0.0062169, 0.010791)  # my.yaml
+    pipe = orbamd.device.BatchPipeline(torch, 640, 480, B)
+    st = pipe.stream_ptr()
+    pipe.extract(torch.from_numpy(orbamd.synth_frames(0, 0, B, 640, 480)).cuda())
+    torch.cuda.synchronize()
+    pipe.check_error()
+    nkp = int(pipe.counts.sum().item())
+    kps_un = torch.empty_like(pipe.kps)
+    kun = torch.empty((B, pipe.stride, 2), dtype=torch.float32, device=pipe.dev)
+    row = {"row": "undistort_batch", "workload": "%d frames 640x480, %d keypoints (%.0f per frame, stride %d), "
+           "my.yaml camera" % (B, nkp, nkp / B, pipe.stride), "launches_per_window": reps}
+    for tag, k, per in (("kun", kun, 56), ("nokun", None, 48)):
+        def run():
+            pipe.ext.undistort_batch_device(cam, pipe.kps, pipe.counts, kps_un, k, st)
+        for _ in range(5):
+            run()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of `reps` launches: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                run()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / reps)
+        t = float(np.median(times))
+        rate = per * nkp / (t * 1e-3)
+        row["%s_bytes_per_launch" % tag] = per * nkp
+        row["%s_ms_per_launch" % tag] = round(t, 5)
+        row["%s_ms_min_max" % tag] = [round(min(times), 5), round(max(times), 5)]
+        row["%s_bytes_per_s" % tag] = round(rate, 0)
+        row["%s_share_of_hbm_peak_8TBps" % tag] = round(rate / HBM_PEAK, 4)
+    # the timed launches computed Frame::UndistortKeyPoints: frame 0 against the host unit
+    from orbamd.frame import undistort_keypoints
+    k0, _ = pipe.host_keypoints(0)
+    got = kps_un[0, :len(k0)].cpu().numpy().copy().view(np.uint8).view(orbamd.kp_dtype).reshape(len(k0))
+    row["frame0_equals_host_unit"] = got.tobytes() == undistort_keypoints(cam, k0).tobytes()
+    assert row["frame0_equals_host_unit"]
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -434,7 +485,8 @@ def main():
     rows = {"extract_host": lambda: bench_extract_host(100), "matcher_host": lambda: bench_matcher_host(100),
             "stereo": lambda: bench_stereo(torch, steps), "projection": lambda: bench_projection(50), "fuse": lambda: bench_fuse(50),
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
-            "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200)}
+            "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200),
+            "undistort": lambda: bench_undistort(torch, 200)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
