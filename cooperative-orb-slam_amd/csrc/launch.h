@@ -86,6 +86,36 @@ hipError_t launch_undistort(const orbx_camera& cam, int nframes, const orbx_kp* 
 hipError_t launch_undistort_deliver(const orbx_camera& cam, const orbx_kp* kps, const int32_t* count, int kp_stride,
                                     orbx_kp* raw_out, orbx_kp* un_out, int32_t* count_out, hipStream_t st);
 
+/* Frame::UnprojectStereo of every frame of a batch (track_kernels.hip); invfx / invfy = 1.0f / fx, 1.0f / fy */
+hipError_t launch_unproject(float cx, float cy, float invfx, float invfy, int nframes, const orbx_kp* kps_un,
+                            const float* depth, const int32_t* counts, int kp_stride, const float* Tcw, float* pos,
+                            uint8_t* mp_flags, int valid_flags, hipStream_t st);
+/* the device-resident inputs of SearchByProjection(CurrentFrame, LastFrame) for a batch of frame pairs, and the
+ * per-pair scratch the prologue (k_track_prologue) points each pair's ProjCall at */
+struct TrackArgs {
+    const int32_t *cur, *last;
+    int nframes;
+    const orbx_kp* kps;
+    const uint8_t* desc;
+    const int32_t* counts;
+    int kp_stride;
+    const float* uright;
+    const uint8_t* occupied;
+    const float* pos;
+    const uint8_t* mp_flags;
+    const float* Tcw;
+    orbm_track_geom g;
+    float th;
+    int mono, check_ori;
+    int32_t *match, *nmatches;
+    int32_t* err;
+    ProjCall* calls;        // [npairs]
+    uint8_t* pair_scratch;  // npairs x pair_bytes, carved per pair at the o_* offsets
+    long long pair_bytes;
+    long long o_x, o_y, o_ang, o_oct, o_q, o_gs, o_gi, o_scan, o_scnt, o_res;
+};
+hipError_t launch_track_prologue(const TrackArgs& a, int pair0, int npairs, hipStream_t st);
+
 hipError_t launch_flag_take(int32_t* flag, int32_t* out, hipStream_t st);
 hipError_t launch_call_done(int32_t* flag, int32_t* out_err, int32_t* seq, int32_t* out_done, hipStream_t st);
 hipError_t launch_pack_slot(const orbx_kf_source& src, const SlotLayout& L, const orbx_kf_meta& meta, uint8_t* slot,

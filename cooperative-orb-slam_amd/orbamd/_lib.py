@@ -34,6 +34,13 @@ class OrbxCamera(C.Structure):
     _fields_ = [(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3")]
 
 
+class OrbmTrackGeom(C.Structure):
+    """orbm_track_geom: the Frame fields SearchByProjection(CurrentFrame, LastFrame) reads, one set per launch."""
+    _fields_ = ([(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "b", "min_x", "min_y", "max_x", "max_y",
+                                          "grid_w_inv", "grid_h_inv")] +
+                [("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)])
+
+
 class OrbmKfView(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
                 ("angle", C.c_void_p), ("octave", C.c_void_p), ("uright", C.c_void_p),
@@ -165,6 +172,10 @@ SIGNATURES = {
     "orbx_set_camera": (_I, [_P, C.POINTER(OrbxCamera)]),
     "orbx_last_keypoints_un": (_I, [_P, _P, _I, C.POINTER(_I)]),
     "orbx_undistort_batch_device": (_I, [_P, C.POINTER(OrbxCamera), _I, _P, _P, _I, _P, _P, _P]),
+    "orbx_unproject_stereo": (_I, [C.POINTER(OrbxCamera), _P, _I, _P, _P, _P, _P]),
+    "orbx_unproject_stereo_batch_device": (_I, [_P, C.POINTER(OrbxCamera), _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
+    "orbm_search_by_projection_last_frame_batch_device": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P,
+                                                               C.POINTER(OrbmTrackGeom), _F, _I, _I, _P, _P, _P]),
     "orbm_search_by_projection_local": (_I, [_P, _P, _P, _F, _F, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_last_frame": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_keyframe": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),

@@ -175,6 +175,58 @@ class BatchPipeline:
             self.fv_off.data_ptr(), self.fv_feat.data_ptr(), self.nfv.data_ptr(), self.max_nodes, float(nnratio),
             int(check_ori), out.data_ptr(), nmatches.data_ptr(), st), "orbm_search_by_bow_batch_device")
 
+    # ---- frame-to-frame tracking (include/orbslam_amd.h "Frame-to-frame tracking on a device batch") ----
+    def track_camera(self):
+        """the orbx_camera the tracking calls use: the pipeline's camera, or my.yaml's without distortion"""
+        from .frame import make_camera
+        return self.camera if self.camera is not None else make_camera((FX, FY, CX, CY, 0, 0, 0, 0))
+
+    def track_geom(self):
+        """orbm_track_geom of this pipeline: its camera (camera=None: my.yaml's, the image's own bounds), the stereo
+        rig's mbf / mb (monocular: 0) and the extractor's scale factors"""
+        from .frame import image_bounds, track_geom
+        if getattr(self, "_track_geom", None) is None:
+            cam = self.track_camera()
+            b, gw, gh = image_bounds(cam, self.W, self.H)
+            mbf, mb = self.stereo if self.stereo else (0.0, 0.0)
+            self._track_geom = track_geom(cam.fx, cam.fy, cam.cx, cam.cy, mbf, mb, b, gw, gh, self.scale)
+        return self._track_geom
+
+    def unproject(self, poses, pos=None, mp_flags=None, valid_flags=9, stream=None):
+        """Frame::UnprojectStereo (Frame.cc:667-681) of every keypoint of the B frames (stereo pipeline: kps_un and
+        depth of the left images) on the device: poses float32 cuda [B, 4, 4] (mTcw); pos float32 cuda [B, stride, 3]
+        (default: self.pos). With mp_flags (uint8 cuda [B, stride]) every row also gets valid_flags for z > 0 and 0
+        otherwise (default 9: a MapPoint with observations, what track_pairs reads). Returns pos."""
+        torch = self.torch
+        if not self.stereo:
+            raise RuntimeError("unproject needs a stereo pipeline (mvDepth)")
+        if pos is None:
+            if getattr(self, "pos", None) is None:
+                self.pos = torch.zeros((self.B, self.stride, 3), dtype=torch.float32, device=self.dev)
+            pos = self.pos
+        st = self.stream_ptr() if stream is None else stream
+        cam = self.track_camera()
+        check(self.lib.orbx_unproject_stereo_batch_device(
+            self.ext._h, C.byref(cam), self.B, self.kps_un.data_ptr(), self.depth.data_ptr(), self.counts.data_ptr(),
+            self.stride, poses.data_ptr(), pos.data_ptr(), mp_flags.data_ptr() if mp_flags is not None else None,
+            int(valid_flags), st), "orbx_unproject_stereo_batch_device")
+        return pos
+
+    def track_pairs(self, cur, last, pos, mp_flags, poses, th, mono, check_ori, out, nmatches, stream=None):
+        """SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1328-1470) of every pair (cur[p],
+        last[p]) over the pipeline's own kps_un, desc, counts and (stereo) uright: cur / last int32 cuda [npairs]
+        (frames 0..B-1); pos float32 [B, stride, 3] and mp_flags uint8 [B, stride] (bit 0 MapPoint, bit 2 outlier,
+        bit 3 observations) of every frame; poses float32 [B, 4, 4]; out int32 [npairs, stride], nmatches int32
+        [npairs]. No feature of a current frame is occupied beforehand (Tracking.cc:879 clears mvpMapPoints)."""
+        st = self.stream_ptr() if stream is None else stream
+        g = self.track_geom()
+        check(self.lib.orbm_search_by_projection_last_frame_batch_device(
+            self.mh, int(cur.numel()), cur.data_ptr(), last.data_ptr(), self.B, self.kps_un.data_ptr(),
+            self.desc.data_ptr(), self.counts.data_ptr(), self.stride,
+            self.uright.data_ptr() if self.stereo else None, None, pos.data_ptr(), mp_flags.data_ptr(), poses.data_ptr(), C.byref(g), float(th), int(bool(mono)),
+            int(bool(check_ori)), out.data_ptr(), nmatches.data_ptr(), st),
+            "orbm_search_by_projection_last_frame_batch_device")
+
     def step(self, frames, stream=None):
         self.extract(frames, stream)
         self.match_pairs(stream)

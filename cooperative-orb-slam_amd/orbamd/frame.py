@@ -7,12 +7,15 @@
   ``Frame::UndistortKeyPoints`` (Frame.cc:405-435) and ``Frame::ComputeImageBounds`` (Frame.cc:437-465, with the
   grid cell sizes of Frame.cc:213-214) on the host; the device batch form is
   ``ORBextractor.undistort_batch_device``.
+* :func:`unproject_stereo` -- ``Frame::UnprojectStereo`` (Frame.cc:667-681) of a frame's keypoints on the host; the
+  device batch form is ``BatchPipeline.unproject``. :func:`track_geom` builds the ``orbm_track_geom`` of
+  ``BatchPipeline.track_pairs``.
 """
 import ctypes as C
 
 import numpy as np
 
-from ._lib import KP_FIELDS, OrbxCamera, check, load
+from ._lib import KP_FIELDS, OrbmTrackGeom, OrbxCamera, check, load
 
 
 def compute_stereo_matches(left, right, kpsL, descL, kpsR, descR, mbf, mb):
@@ -93,3 +96,35 @@ def image_bounds(camera, cols, rows):
     check(load().orbx_image_bounds(C.byref(cam), int(cols), int(rows), b.ctypes.data, C.byref(gw), C.byref(gh)),
           "orbx_image_bounds")
     return b, np.float32(gw.value), np.float32(gh.value)
+
+
+def unproject_stereo(camera, Tcw, kps_un, depth):
+    """Frame::UnprojectStereo (Frame.cc:667-681) of every keypoint: kps_un = mvKeysUn (structured array of kp_dtype),
+    depth = mvDepth float32 [n], Tcw = mTcw 4x4. Returns (pos float32 [n, 3], valid uint8 [n]); z <= 0 gives three
+    zeros and valid 0. Only fx, fy, cx, cy of the camera are read."""
+    kps = np.ascontiguousarray(kps_un, np.dtype(KP_FIELDS))
+    n = len(kps)
+    depth = np.ascontiguousarray(depth, np.float32).reshape(n)
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    pos = np.empty((n, 3), np.float32)
+    valid = np.empty(n, np.uint8)
+    cam = make_camera(camera)
+    check(load().orbx_unproject_stereo(C.byref(cam), T.ctypes.data, n, kps.ctypes.data, depth.ctypes.data,
+                                       pos.ctypes.data, valid.ctypes.data), "orbx_unproject_stereo")
+    return pos, valid
+
+
+def track_geom(fx, fy, cx, cy, bf, b, bounds, grid_w_inv, grid_h_inv, scale_factors):
+    """orbm_track_geom: camera, mbf, mb, (mnMinX, mnMaxX, mnMinY, mnMaxY) and the grid inverses as image_bounds returns
+    them, mvScaleFactors."""
+    s = np.asarray(scale_factors, np.float32)
+    if not 1 <= len(s) <= 16:
+        raise ValueError("1 to 16 scale factors")
+    g = OrbmTrackGeom()
+    g.fx, g.fy, g.cx, g.cy, g.bf, g.b = (float(np.float32(v)) for v in (fx, fy, cx, cy, bf, b))
+    g.min_x, g.max_x, g.min_y, g.max_y = (float(np.float32(v)) for v in bounds)
+    g.grid_w_inv, g.grid_h_inv = float(np.float32(grid_w_inv)), float(np.float32(grid_h_inv))
+    g.nlevels = len(s)
+    for i, v in enumerate(s):
+        g.scale_factors[i] = float(v)
+    return g

@@ -831,6 +831,81 @@ int orbx_set_camera(orbx_handle* h, const orbx_camera* cam);
 int orbx_last_keypoints_un(orbx_handle* h, orbx_kp* kps_un, int cap, int* n);
 
 /* ------------------------------------------------------------------------------------
+ * Frame-to-frame tracking on a device batch: Frame::UnprojectStereo (ORB_SLAM2/src/Frame.cc:
+ * 667-681) and ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono)
+ * (ORBmatcher.cc:1328-1470) as Tracking::TrackWithMotionModel calls it (Tracking.cc:869-900),
+ * over frames that already sit in HBM.
+ * ---------------------------------------------------------------------------------- */
+
+/* Frame::UnprojectStereo (Frame.cc:667-681) of keypoints 0..n-1 of one frame on the host:
+ * pos[3 i .. +3) = mRwc * x3Dc + mOw with x3Dc = ((u - cx) z invfx, (v - cy) z invfy, z), (u, v) =
+ * kps_un[i] (mvKeysUn), z = depth[i] (mvDepth), invfx = 1.0f / fx (Frame.cc:104-105), mRwc = mRcw.t()
+ * and mOw = -mRcw.t() * mtcw of Tcw (mTcw, 4x4 row-major; Frame.cc:261-267), in cv::Mat's float
+ * arithmetic (DESIGN.md "Pinned semantics"). z <= 0 (the reference returns cv::Mat()): three zeros,
+ * valid[i] = 0; otherwise valid[i] = 1 (valid may be NULL). Only fx, fy, cx, cy of cam are read.
+ * Host only, no device. ORBX_EARG on NULL arguments, n < 0 or fx == 0 || fy == 0, before anything
+ * is written. */
+int orbx_unproject_stereo(const orbx_camera* cam, const float Tcw[16], int n, const orbx_kp* kps_un,
+                          const float* depth, float* pos, uint8_t* valid);
+
+/* The same for every frame of a device batch: frame f's keypoints, depths and outputs at
+ * f*kp_stride (d_kps_un: orbx_undistort_batch_device's output or, without distortion, the
+ * extractor's; d_depth: orbx_stereo_matches_batch_device's), its count d_counts[f] (clamped to
+ * kp_stride) and its pose d_Tcw[16 f .. +16); mOw is derived per frame on the device, so a captured
+ * graph can be replayed with new poses. Rows i >= d_counts[f] are not written. With d_mp_flags (not
+ * NULL) row i also gets valid_flags for z > 0 and 0 otherwise: the flags
+ * orbm_search_by_projection_last_frame_batch_device reads. Bit-identical to the host form. d_kps_un
+ * must be 8-byte aligned, nframes <= 65535. Enqueued on `stream`; no host sync. */
+int orbx_unproject_stereo_batch_device(orbx_handle* h, const orbx_camera* cam, int nframes,
+                                       const orbx_kp* d_kps_un, const float* d_depth,
+                                       const int32_t* d_counts, int kp_stride, const float* d_Tcw,
+                                       float* d_pos, uint8_t* d_mp_flags, int valid_flags,
+                                       void* stream);
+
+/* The Frame fields SearchByProjection(CurrentFrame, LastFrame, ...) reads, one set per launch. */
+typedef struct orbm_track_geom {
+    float fx, fy, cx, cy, bf, b;                                /* camera, mbf, mb                */
+    float min_x, min_y, max_x, max_y, grid_w_inv, grid_h_inv;   /* orbx_image_bounds              */
+    int32_t nlevels;                                            /* mnScaleLevels, 1..16           */
+    float scale_factors[16];                                    /* mvScaleFactors                 */
+} orbm_track_geom;
+
+/* ORBmatcher::SearchByProjection(CurrentFrame, LastFrame, th, bMono) (ORBmatcher.cc:1328-1470) for
+ * npairs frame pairs of one device batch: pair p is the reference call with CurrentFrame = frame
+ * d_cur[p] and LastFrame = frame d_last[p]. Per frame f (everything at f*kp_stride, count
+ * d_counts[f]): d_kps_un = mvKeysUn, d_desc = mDescriptors, d_uright = mvuRight (NULL = monocular,
+ * all -1), d_occupied[i] != 0 = CurrentFrame.mvpMapPoints[i] with Observations() > 0 before the call
+ * (NULL = none, as after Tracking.cc:879), d_pos = the world position of feature i's MapPoint
+ * (n x 3), d_Tcw[16 f .. +16) = mTcw (row-major), and d_mp_flags of feature i:
+ *   bit 0  the feature has a MapPoint (as in orbm_search_by_bow_batch_device);
+ *   bit 1  that MapPoint is bad: the reference does not test it here, ignored;
+ *   bit 2  LastFrame.mvbOutlier[i];
+ *   bit 3  Observations() > 0: a match occupies the feature for the queries after it.
+ * Feature i of the last frame is a query iff bit 0 is set and bit 2 is clear (ORBmatcher.cc:1355-
+ * 1359); its octave and angle are d_kps_un's, its descriptor its d_desc row. A device prologue does
+ * the per-MapPoint geometry of ORBmatcher.cc:1339-1405 with the per-call entry's float semantics
+ * and fills one search call per pair in the ctx's scratch; the grid, scan and in-order resolve
+ * kernels of the per-call entry then run once each over all pairs.
+ * Output as for every variant: d_match[p*kp_stride + i], i < d_counts[d_cur[p]], = the last-frame
+ * feature index, -1 or -2; d_nmatches[p] = the reference's return value.
+ * Validation on the device: a current frame's count is clamped to kp_stride; a pair with a frame
+ * index outside [0, nframes), a last-frame count above kp_stride or an accepted feature whose
+ * octave is outside [0, nlevels) raises the ctx's error flag (orbm_check_error), gets nmatches = 0
+ * and -1 in its whole d_match row, and reads nothing out of range; the other pairs are unaffected.
+ * ORBX_EARG for NULL arguments, npairs < 0, nframes < 1, kp_stride outside [1, 65536], nlevels
+ * outside [1, 16] or d_kps_un / d_desc not 8- / 16-byte aligned; npairs == 0 (with a valid ctx, geom
+ * and sizes; the arrays may then be NULL) is a no-op that returns 0.
+ * The call only enqueues on `stream` (no upload, no host wait); the ctx's scratch grows at the first
+ * call of a larger npairs x kp_stride (an allocation: not inside a stream capture). One ctx serves
+ * one stream at a time. */
+int orbm_search_by_projection_last_frame_batch_device(
+    orbm_ctx* ctx, int npairs, const int32_t* d_cur, const int32_t* d_last, int nframes,
+    const orbx_kp* d_kps_un, const uint8_t* d_desc, const int32_t* d_counts, int kp_stride,
+    const float* d_uright, const uint8_t* d_occupied, const float* d_pos, const uint8_t* d_mp_flags,
+    const float* d_Tcw, const orbm_track_geom* geom, float th, int mono, int check_ori,
+    int32_t* d_match, int32_t* d_nmatches, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Synthetic input: deterministic frame t of agent a, width x height,
  * written to host out (pitch = width). Identical on every machine (integer-only).
  * ---------------------------------------------------------------------------------- */

@@ -26,6 +26,12 @@
                1024-frame C2 extraction (640x480, 1000 features, my.yaml's distorted camera), with and without the
                `kun` output: kernel time from HIP events around 200 launches (median of five windows, min-max), and the
                bytes moved (sum of counts x 48 B, + 8 B with kun) over it as a share of the HBM peak.
+  track        Frame-to-frame tracking on C2's shape (640x480 stereo, 1000 features): one 1280-frame stereo batch
+               resident in HBM, Frame::UnprojectStereo of every keypoint (orbx_unproject_stereo_batch_device, depths
+               and flags from the stereo batch) and SearchByProjection(frame f + 1, frame f) for the 1279 consecutive
+               pairs in one launch (orbm_search_by_projection_last_frame_batch_device), each alone from HIP events
+               (median of five windows, min-max), vs the per-call orbm_search_by_projection_last_frame over the same
+               pairs from host arrays (wall clock around the calls); the two must agree on every pair.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -478,6 +484,88 @@ def bench_undistort(torch, reps):
     return row
 
 
+def bench_track(torch, reps, B=1280):
+    import orbamd
+    from orbamd.device import STEREO_RIGS, BatchPipeline
+    W, H = 640, 480
+    rig = STEREO_RIGS["euroc"]
+    pipe = BatchPipeline(torch, W, H, B, nfeatures=1000, stereo=rig)
+    dev, S = pipe.dev, pipe.stride
+    left = orbamd.synth_frames(0, 0, B, W, H)
+    right = orbamd.synth_frames(0, 0, B, W, H, dx=8)
+    pipe.extract(torch.from_numpy(np.concatenate([left, right])).to(dev))
+    torch.cuda.synchronize()
+    pipe.check_error()
+    rng = np.random.default_rng(1)
+    poses = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    poses[:, :3, 3] = np.cumsum(rng.normal(0, 0.005, (B, 3)), 0).astype(np.float32)  # a slow drift
+    tposes = torch.from_numpy(poses).to(dev)
+    flags = torch.zeros((B, S), dtype=torch.uint8, device=dev)
+    cur = torch.arange(1, B, dtype=torch.int32, device=dev)
+    last = torch.arange(0, B - 1, dtype=torch.int32, device=dev)
+    out = torch.empty((B - 1, S), dtype=torch.int32, device=dev)
+    nm = torch.zeros(B - 1, dtype=torch.int32, device=dev)
+    th, mono, ori = 7.0, False, True  # Tracking.cc:871-877: th = 7 for a stereo camera
+    pos = pipe.unproject(tposes, mp_flags=flags)
+
+    def windows(fn, n):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of n launches: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / n)
+        return float(np.median(times)), min(times), max(times)
+    t_un = windows(lambda: pipe.unproject(tposes, mp_flags=flags), 10 * reps)
+    t_tr = windows(lambda: pipe.track_pairs(cur, last, pos, flags, tposes, th, mono, ori, out, nm), reps)
+    pipe.check_match_error()
+    # the per-call entry over the same pairs, from host copies of the same arrays
+    counts = pipe.counts[:B].cpu().numpy()
+    kall = pipe.kps_un[:B].cpu().numpy().copy().view(np.uint8).view(orbamd.kp_dtype).reshape(B, S)
+    dall, uall = pipe.desc[:B].cpu().numpy(), pipe.uright.cpu().numpy()
+    pall, fall = pos.cpu().numpy(), flags.cpu().numpy()
+    g = pipe.track_geom()
+    views, mps = [], []
+    for f in range(B):
+        n = int(counts[f])
+        F = orbamd.FrameView(kall[f, :n], dall[f, :n], pipe.scale, W, H, g.fx, g.fy, g.cx, g.cy, bf=g.bf,
+                             uright=uall[f, :n])
+        F.b = np.float32(g.b)
+        views.append(F)
+        mps.append(orbamd.MapPoints(n, desc=dall[f, :n], pos=pall[f, :n], has_obs=(fall[f, :n] & 8) != 0,
+                                    skip=(fall[f, :n] & 1) == 0, octave=kall[f, :n]["octave"],
+                                    angle=kall[f, :n]["angle"]))
+    mt = orbamd.ORBmatcher(0.9, ori)
+    for f in range(3):
+        mt.SearchByProjectionLastFrame(views[f + 1], poses[f + 1], mps[f], poses[f], th, mono)
+    res = []
+    t0 = time.perf_counter()
+    for f in range(B - 1):
+        res.append(mt.SearchByProjectionLastFrame(views[f + 1], poses[f + 1], mps[f], poses[f], th, mono))
+    t_call = time.perf_counter() - t0
+    mt.close()
+    out_h, nm_h = out.cpu().numpy(), nm.cpu().numpy()
+    same = all(res[f][0] == nm_h[f] and np.array_equal(res[f][1], out_h[f, :len(res[f][1])]) for f in range(B - 1))
+    nkp = int(counts.sum())
+    row = {"row": "track", "workload": "C2 640x480 stereo, 1000 feat, %d frames (%.0f keypoints per frame, stride %d), "
+           "%d consecutive pairs, th %.0f, check_ori" % (B, nkp / B, S, B - 1, th),
+           "unproject_ms_per_launch": round(t_un[0], 5), "unproject_ms_min_max": [round(t_un[1], 5), round(t_un[2], 5)],
+           "unproject_ns_per_keypoint": round(t_un[0] * 1e6 / nkp, 4),
+           "track_ms_per_launch": round(t_tr[0], 4), "track_ms_min_max": [round(t_tr[1], 4), round(t_tr[2], 4)],
+           "track_us_per_pair": round(t_tr[0] * 1e3 / (B - 1), 3),
+           "per_call_ms_all_pairs": round(t_call * 1e3, 2), "per_call_us_per_pair": round(t_call * 1e6 / (B - 1), 2),
+           "matches_per_pair": round(float(nm_h.mean()), 1), "batch_equals_per_call": bool(same)}
+    assert same and nm_h.mean() > 50
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -486,7 +574,7 @@ def main():
             "stereo": lambda: bench_stereo(torch, steps), "projection": lambda: bench_projection(50), "fuse": lambda: bench_fuse(50),
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
             "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200),
-            "undistort": lambda: bench_undistort(torch, 200)}
+            "undistort": lambda: bench_undistort(torch, 200), "track": lambda: bench_track(torch, 10)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
