@@ -116,6 +116,39 @@ struct TrackArgs {
 };
 hipError_t launch_track_prologue(const TrackArgs& a, int pair0, int npairs, hipStream_t st);
 
+/* Frame::isInFrustum of a device table of M MapPoints under nframes poses (local_kernels.hip), outputs at f*M + m */
+hipError_t launch_frustum(const orbm_track_geom& g, float log_scale_factor, float cos_limit, int M, const float* pos,
+                          const float* normal, const float* min_dist, const float* max_dist, int nframes,
+                          const float* Tcw, uint8_t* in_view, float* proj_x, float* proj_y, float* proj_xr,
+                          int32_t* level, float* view_cos, int32_t* err, hipStream_t st);
+/* the device-resident inputs of Tracking::SearchLocalPoints for every frame of a batch, and the per-frame scratch the
+ * prologue (k_local_prologue) points each frame's ProjCall at */
+struct LocalArgs {
+    const orbx_kp* kps;
+    const uint8_t* desc;
+    const int32_t* counts;
+    int kp_stride;
+    const float* uright;
+    const float* Tcw;
+    orbm_track_geom g;
+    float log_scale_factor;
+    int M;  // the local-map table
+    const float *pos, *normal, *min_dist, *max_dist;
+    const uint8_t *mp_desc, *mp_flags;
+    const int32_t* range;     // [2 nframes] or nullptr
+    const int32_t* frame_mp;  // [nframes x kp_stride]
+    float th, nnratio, cos_limit;
+    int32_t *match, *nmatches, *ntomatch;
+    uint8_t* in_view;  // [nframes x M] or nullptr
+    int32_t* err;
+    ProjCall* calls;         // [nframes]
+    uint8_t* frame_scratch;  // nframes x frame_bytes, carved per frame at the o_* offsets
+    long long frame_bytes;
+    long long o_x, o_y, o_oct, o_occ, o_seen, o_q, o_gs, o_gi, o_scan, o_scnt, o_res;
+};
+/* k_local_prologue then k_local_frustum for frames [frame0, frame0 + nframes) */
+hipError_t launch_local_points(const LocalArgs& a, int frame0, int nframes, hipStream_t st);
+
 hipError_t launch_flag_take(int32_t* flag, int32_t* out, hipStream_t st);
 hipError_t launch_call_done(int32_t* flag, int32_t* out_err, int32_t* seq, int32_t* out_done, hipStream_t st);
 hipError_t launch_pack_slot(const orbx_kf_source& src, const SlotLayout& L, const orbx_kf_meta& meta, uint8_t* slot,

@@ -10,6 +10,9 @@
  *    sincosf algorithm (sysdeps/ieee754/flt-32/s_sinf.c, s_cosf.c): double evaluation,
  *    constants read from libm's __sincosf_table. Verified equal to the host libm (both the
  *    FMA and the SSE2 ifunc variants) for every float in [0, 2*pi] (tools/check_trig.c).
+ *  - glibc_logf: the float log of MapPoint::PredictScale (MapPoint.cc:385-417, inside Frame::isInFrustum). Restated
+ *    from glibc 2.35's logf (sysdeps/ieee754/flt-32/e_logf.c), constants read from libm's __logf_data. Verified
+ *    equal to the host libm for every positive normal float (tools/check_logf.c).
  *  - fast_atan2: cv::fastAtan2 (OpenCV 3.x scalar form), called by IC_Angle
  *    (ORBextractor.cc:103).
  */
@@ -101,6 +104,45 @@ __device__ __forceinline__ void glibc_sincosf(float y, float* s_out, float* c_ou
         *s_out = sinf_poly(xs, x2);
         *c_out = cosf_poly(x2, neg);
     }
+}
+
+/* glibc 2.35 logf (sysdeps/ieee754/flt-32/e_logf.c), the log of MapPoint::PredictScale (MapPoint.cc:385-417, `log`
+ * of a float = logf): __logf_data's {invc, logc} table, ln2 and polynomial read from libm's .rodata; double
+ * evaluation without contraction, one rounding. Equal to the host libm (FMA and plain ifunc variants) for every
+ * positive normal float (tools/check_logf.c, which states the same sequence in C). */
+static __constant__ double kLogfTab[16][2] = {
+    {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
+    {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
+    {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
+    {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
+    {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
+    {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
+    {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3},
+    {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2}};
+#define LOGF_LN2 0x1.62e42fefa39efp-1
+#define LOGF_A0 -0x1.00ea348b88334p-2
+#define LOGF_A1 0x1.5575b0be00b6ap-2
+#define LOGF_A2 -0x1.ffffef20a4123p-2
+
+/* a positive normal float (0x00800000 <= bits < 0x7f800000); anything else is the caller's to exclude */
+__device__ __forceinline__ bool logf_domain(float x) {
+    return __float_as_uint(x) - 0x00800000u < 0x7f800000u - 0x00800000u;
+}
+__device__ __forceinline__ float glibc_logf(float x) {
+    const uint32_t ix = __float_as_uint(x);
+    if (ix == 0x3f800000u) return 0.0f;
+    const uint32_t tmp = ix - 0x3f330000u;
+    const int i = (tmp >> 19) & 15;
+    const int k = (int32_t)tmp >> 23;
+    const double z = (double)__uint_as_float(ix - (tmp & 0xff800000u));
+    const double invc = kLogfTab[i][0], logc = kLogfTab[i][1];
+    const double r = __dadd_rn(__dmul_rn(z, invc), -1.0);
+    const double y0 = __dadd_rn(logc, __dmul_rn((double)k, LOGF_LN2));
+    const double r2 = __dmul_rn(r, r);
+    double y = __dadd_rn(__dmul_rn(LOGF_A1, r), LOGF_A2);
+    y = __dadd_rn(__dmul_rn(LOGF_A0, r2), y);
+    y = __dadd_rn(__dmul_rn(y, r2), __dadd_rn(y0, r));
+    return __double2float_rn(y);
 }
 
 }  // namespace orbamd

@@ -52,6 +52,10 @@ int orbx_describe_blur_fused(const void* frames, size_t frame_stride, size_t pit
  * ORBextractor.cc:113) applied to n device floats; lets tests compare against host libm. */
 int orbx_selftest_sincosf(const float* d_in, float* d_sin, float* d_cos, int n, void* stream);
 
+/* Test hook: the device's restatement of glibc logf (MapPoint::PredictScale, MapPoint.cc:385-417) applied to n device
+ * floats; an input that is not a positive normal float (outside the restatement's domain) gives a quiet NaN. */
+int orbx_selftest_logf(const float* d_in, float* d_out, int n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

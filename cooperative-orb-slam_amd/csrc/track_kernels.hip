@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "extract_host.h"
+#include "frame_math.h"
 #include "matcher_host.h"
 
 namespace orbamd {
@@ -21,20 +22,6 @@ namespace {
 
 constexpr int kUnprojectThreads = 256;
 constexpr int kTrackThreads = 256;
-
-/* (A x)[r] + c of the small-matrix gemm: a0 x0 + a1 x1 + a2 x2 in float, then (float)((double)t + (double)c) */
-__device__ __forceinline__ float gemm_row(float a0, float a1, float a2, float x0, float x1, float x2, float c) {
-    const float t = __fadd_rn(__fadd_rn(__fmul_rn(a0, x0), __fmul_rn(a1, x1)), __fmul_rn(a2, x2));
-    return __double2float_rn(__dadd_rn((double)t, (double)c));
-}
-
-/* (-A.t() x)[i] of a row-major 3x4 [R | t] block (GEMM_1_T): s = 0; s += (double)A[k][i] * (double)x[k]; -1.0 * s */
-__device__ __forceinline__ float gemm_t_neg(const float* T, int i, float x0, float x1, float x2) {
-    double s = __dadd_rn(0.0, __dmul_rn((double)T[i], (double)x0));
-    s = __dadd_rn(s, __dmul_rn((double)T[4 + i], (double)x1));
-    s = __dadd_rn(s, __dmul_rn((double)T[8 + i], (double)x2));
-    return __double2float_rn(__dmul_rn(-1.0, s));
-}
 
 /* grid (ceil(kp_stride / kUnprojectThreads), nframes), one lane per keypoint. The first 8 bytes of the 24-byte
  * orbx_kp record are (x, y). */

@@ -176,6 +176,11 @@ SIGNATURES = {
     "orbx_unproject_stereo_batch_device": (_I, [_P, C.POINTER(OrbxCamera), _I, _P, _P, _P, _I, _P, _P, _P, _I, _P]),
     "orbm_search_by_projection_last_frame_batch_device": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _P, _P,
                                                                C.POINTER(OrbmTrackGeom), _F, _I, _I, _P, _P, _P]),
+    "orbx_is_in_frustum": (_I, [C.POINTER(OrbmTrackGeom), _F, _P, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "orbx_is_in_frustum_batch_device": (_I, [_P, C.POINTER(OrbmTrackGeom), _F, _F, _I, _P, _P, _P, _P, _I, _P, _P, _P,
+                                             _P, _P, _P, _P, _P]),
+    "orbm_search_local_points_batch_device": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, C.POINTER(OrbmTrackGeom), _F, _I,
+                                                   _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
     "orbm_search_by_projection_local": (_I, [_P, _P, _P, _F, _F, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_last_frame": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_keyframe": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
@@ -215,6 +220,7 @@ SIGNATURES = {
     "orbdb_select_candidates": (_I, [_I, _I, _P, _P, _P, _P, _P, _P, _F, _P, _P, C.POINTER(_I)]),
     "orbm_compute_distinctive_descriptors_device": (_I, [_P, _I, _P, _P, _P, _P, _P]),
     "orbx_selftest_sincosf": (_I, [_P, _P, _P, _I, _P]),
+    "orbx_selftest_logf": (_I, [_P, _P, _I, _P]),
     "orbx_profile_enable": (_I, [_P, _I]),
     "orbx_profile_read": (_I, [_P, C.POINTER(C.c_double), C.POINTER(_I)]),
     "orbx_version": (C.c_char_p, []),

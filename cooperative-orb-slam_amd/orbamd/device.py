@@ -227,6 +227,49 @@ class BatchPipeline:
             int(bool(check_ori)), out.data_ptr(), nmatches.data_ptr(), st),
             "orbm_search_by_projection_last_frame_batch_device")
 
+    # ---- local-map tracking (include/orbslam_amd.h "Local-map tracking on a device batch") ----
+    def log_scale_factor(self):
+        """mfLogScaleFactor = log(mfScaleFactor) of the pipeline's extractor (Frame.cc:72), as a float"""
+        import math
+        return float(np.float32(math.log(float(np.float32(self.ext.GetScaleFactor())))))
+
+    def frustum(self, poses, pos, normal, min_dist, max_dist, viewing_cos_limit=0.5, stream=None):
+        """Frame::isInFrustum (Frame.cc:274-330) of a device table of M MapPoints under each of the nf poses (float32
+        cuda [nf, 4, 4]): pos / normal float32 cuda [M, 3], min_dist / max_dist float32 cuda [M] (raw mfMinDistance /
+        mfMaxDistance). Returns the six tracking arrays as cuda tensors [nf, M]: (in_view uint8, proj_x, proj_y,
+        proj_xr float32, level int32, view_cos float32)."""
+        torch = self.torch
+        nf, M = int(poses.shape[0]), int(pos.shape[0])
+        z = lambda dt: torch.zeros((nf, M), dtype=dt, device=self.dev)  # noqa: E731
+        out = (z(torch.uint8), z(torch.float32), z(torch.float32), z(torch.float32), z(torch.int32), z(torch.float32))
+        st = self.stream_ptr() if stream is None else stream
+        g = self.track_geom()
+        check(self.lib.orbx_is_in_frustum_batch_device(
+            self.mh, C.byref(g), self.log_scale_factor(), float(viewing_cos_limit), M, pos.data_ptr(),
+            normal.data_ptr(), min_dist.data_ptr(), max_dist.data_ptr(), nf, poses.data_ptr(),
+            *[t.data_ptr() for t in out], st), "orbx_is_in_frustum_batch_device")
+        return out
+
+    def track_local(self, poses, pos, normal, min_dist, max_dist, mp_desc, mp_flags, frame_mp, th, out, nmatches,
+                    ntomatch, ranges=None, in_view=None, nnratio=0.8, viewing_cos_limit=0.5, stream=None):
+        """Tracking::SearchLocalPoints (Tracking.cc:1143-1193) of the B frames over the pipeline's own kps_un, desc,
+        counts and (stereo) uright: poses float32 cuda [B, 4, 4]; the local-map table pos / normal float32 [M, 3],
+        min_dist / max_dist float32 [M], mp_desc uint8 [M, 32], mp_flags uint8 [M] (bit 1 bad, bit 3 observations);
+        frame_mp int32 [B, stride] = the table index of every feature's MapPoint or -1 (e.g. mapped from track_pairs'
+        match rows); ranges int32 [B, 2] = each frame's slice of the table (None: all of it); out int32 [B, stride],
+        nmatches / ntomatch int32 [B]; in_view uint8 [B, M] (optional). th = 1, 3 (RGB-D) or 5 (after a
+        relocalisation); nnratio = the ORBmatcher's (0.8 in SearchLocalPoints)."""
+        st = self.stream_ptr() if stream is None else stream
+        g = self.track_geom()
+        M = int(pos.shape[0])
+        check(self.lib.orbm_search_local_points_batch_device(
+            self.mh, self.B, self.kps_un.data_ptr(), self.desc.data_ptr(), self.counts.data_ptr(), self.stride,
+            self.uright.data_ptr() if self.stereo else None, poses.data_ptr(), C.byref(g), self.log_scale_factor(), M,
+            pos.data_ptr(), normal.data_ptr(), min_dist.data_ptr(), max_dist.data_ptr(), mp_desc.data_ptr(),
+            mp_flags.data_ptr(), ranges.data_ptr() if ranges is not None else None, frame_mp.data_ptr(), float(th),
+            float(nnratio), float(viewing_cos_limit), out.data_ptr(), nmatches.data_ptr(), ntomatch.data_ptr(),
+            in_view.data_ptr() if in_view is not None else None, st), "orbm_search_local_points_batch_device")
+
     def step(self, frames, stream=None):
         self.extract(frames, stream)
         self.match_pairs(stream)

@@ -10,6 +10,9 @@
 * :func:`unproject_stereo` -- ``Frame::UnprojectStereo`` (Frame.cc:667-681) of a frame's keypoints on the host; the
   device batch form is ``BatchPipeline.unproject``. :func:`track_geom` builds the ``orbm_track_geom`` of
   ``BatchPipeline.track_pairs``.
+* :func:`is_in_frustum` -- ``Frame::isInFrustum`` (Frame.cc:274-330, with ``MapPoint::PredictScale``) of a table of
+  MapPoints on the host; the device batch forms are ``BatchPipeline.frustum`` and, inside
+  ``Tracking::SearchLocalPoints``, ``BatchPipeline.track_local``.
 """
 import ctypes as C
 
@@ -128,3 +131,24 @@ def track_geom(fx, fy, cx, cy, bf, b, bounds, grid_w_inv, grid_h_inv, scale_fact
     for i, v in enumerate(s):
         g.scale_factors[i] = float(v)
     return g
+
+
+def is_in_frustum(geom, log_scale_factor, Tcw, pos, normal, min_dist, max_dist, viewing_cos_limit=0.5):
+    """Frame::isInFrustum (Frame.cc:274-330) of n MapPoints under the pose Tcw (mTcw 4x4): geom = an orbm_track_geom
+    (track_geom), log_scale_factor = mfLogScaleFactor, pos / normal float32 [n, 3], min_dist / max_dist float32 [n] (the
+    raw mfMinDistance / mfMaxDistance). Returns the six tracking arrays of MapPoints: (in_view uint8, proj_x, proj_y,
+    proj_xr float32, level int32, view_cos float32), each [n]; a rejected point has in_view 0 and zeros."""
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    n = len(pos)
+    normal = np.ascontiguousarray(normal, np.float32).reshape(n, 3)
+    mind = np.ascontiguousarray(min_dist, np.float32).reshape(n)
+    maxd = np.ascontiguousarray(max_dist, np.float32).reshape(n)
+    T = np.ascontiguousarray(Tcw, np.float32).reshape(16)
+    in_view = np.empty(n, np.uint8)
+    x, y, xr, vc = (np.empty(n, np.float32) for _ in range(4))
+    level = np.empty(n, np.int32)
+    check(load().orbx_is_in_frustum(C.byref(geom), float(log_scale_factor), T.ctypes.data, float(viewing_cos_limit), n,
+                                    pos.ctypes.data, normal.ctypes.data, mind.ctypes.data, maxd.ctypes.data,
+                                    in_view.ctypes.data, x.ctypes.data, y.ctypes.data, xr.ctypes.data,
+                                    level.ctypes.data, vc.ctypes.data), "orbx_is_in_frustum")
+    return in_view, x, y, xr, level, vc

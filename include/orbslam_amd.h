@@ -906,6 +906,92 @@ int orbm_search_by_projection_last_frame_batch_device(
     int32_t* d_match, int32_t* d_nmatches, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Local-map tracking on a device batch: Frame::isInFrustum (Frame.cc:274-330, with
+ * MapPoint::PredictScale, MapPoint.cc:385-417) and Tracking::SearchLocalPoints
+ * (Tracking.cc:1143-1193) with its ORBmatcher::SearchByProjection(F, vpMapPoints, th)
+ * (ORBmatcher.cc:45-129), as Tracking::TrackLocalMap runs them on every frame.
+ * ---------------------------------------------------------------------------------- */
+
+/* Frame::isInFrustum(pMP, viewingCosLimit) of n MapPoints on the host, under the pose Tcw (mTcw, 4x4
+ * row-major). Of geom: fx, fy, cx, cy, bf, the bounds and nlevels are read; log_scale_factor =
+ * mfLogScaleFactor. Per point: pos (GetWorldPos, n x 3), normal (GetNormal, n x 3), min_dist / max_dist =
+ * the raw mfMinDistance / mfMaxDistance (the 0.8f / 1.2f of Get*DistanceInvariance are applied here).
+ * Outputs, the six tracking arrays of orbm_mappoints: in_view = mbTrackInView, proj_x / proj_y /
+ * proj_xr = mTrackProjX / Y / XR, level = mnTrackScaleLevel, view_cos = mTrackViewCos; a rejected point
+ * gets in_view = 0 and zeros. The float sequence, in cv::Mat's arithmetic (DESIGN.md "Pinned semantics"):
+ *   Pc = mRcw * P + mtcw (small-matrix gemm); PcZ < 0.0f rejects; invz = 1.0f / PcZ (a float divide);
+ *   u = fx * PcX * invz + cx, v = fy * PcY * invz + cy (float, left to right);
+ *   u < min_x || u > max_x || v < min_y || v > max_y rejects;
+ *   mOw = -mRcw.t() * mtcw (GEMM_1_T, double accumulation); PO = P - mOw (float);
+ *   dist = (float)sqrt(sum (double)PO^2); dist < 0.8f * min_dist || dist > 1.2f * max_dist rejects;
+ *   viewCos = (float)(dot_double(PO, Pn) / (double)dist); viewCos < viewing_cos_limit rejects;
+ *   ratio = max_dist / dist; level = ceilf(logf(ratio) / log_scale_factor) (a float divide, glibc's
+ *   logf) clamped to [0, nlevels - 1]; proj_xr = u - bf * invz.
+ * Contract: where the reference's behaviour is undefined or meaningless the point is rejected -- a
+ * non-finite pose entry or point field, a non-finite Pc, u, v, dist or viewCos, PcZ == +-0, dist == 0,
+ * a ratio that is not a positive normal float.
+ * Host only, no device. ORBX_EARG on NULL arguments, n < 0, nlevels outside [1, 16], a
+ * log_scale_factor that is not finite and > 0 or a non-finite limit, before anything is written. */
+int orbx_is_in_frustum(const orbm_track_geom* geom, float log_scale_factor, const float Tcw[16],
+                       float viewing_cos_limit, int n, const float* pos, const float* normal,
+                       const float* min_dist, const float* max_dist, uint8_t* in_view, float* proj_x,
+                       float* proj_y, float* proj_xr, int32_t* level, float* view_cos);
+
+/* The same for a device table of M points under nframes poses d_Tcw[16 f .. +16) (the layout
+ * orbx_unproject_stereo_batch_device reads): every output at f*M + m. Bit-identical to the host form. A
+ * point the contract excludes also raises the ctx's device error flag (orbm_check_error). M == 0 or
+ * nframes == 0 is a no-op; nframes <= 65535. Enqueued on `stream`; no host sync, no scratch. */
+int orbx_is_in_frustum_batch_device(orbm_ctx* ctx, const orbm_track_geom* geom, float log_scale_factor,
+                                    float viewing_cos_limit, int M, const float* d_pos,
+                                    const float* d_normal, const float* d_min_dist,
+                                    const float* d_max_dist, int nframes, const float* d_Tcw,
+                                    uint8_t* d_in_view, float* d_proj_x, float* d_proj_y,
+                                    float* d_proj_xr, int32_t* d_level, float* d_view_cos, void* stream);
+
+/* Tracking::SearchLocalPoints (Tracking.cc:1143-1193) for every frame of a device batch. The frame
+ * arrays are those of orbm_search_by_projection_last_frame_batch_device (d_kps_un, d_desc, d_counts,
+ * kp_stride, d_uright or NULL, d_Tcw, geom); log_scale_factor = mfLogScaleFactor. The local map is a
+ * table of M MapPoints: d_pos, d_normal (M x 3), d_min_dist, d_max_dist (raw, as above), d_mp_desc
+ * (M x 32, 16-byte aligned) and d_mp_flags with the bits' usual meaning (bit 1 isBad(), bit 3
+ * Observations() > 0, the others ignored). Frame f's mvpLocalMapPoints is the slice
+ * [d_range[2f], d_range[2f+1]) of the table (d_range NULL: the whole table), so the maps of several
+ * agents or windows can share one table. d_frame_mp[f*kp_stride + i] = the table index of feature i's
+ * MapPoint (mCurrentFrame.mvpMapPoints, e.g. from the last-frame search's match row) or negative.
+ * Per frame, on the device:
+ *   - the first loop (:1146-1162): a feature whose MapPoint is bad counts as having none; any other
+ *     MapPoint is marked seen for this frame (mnLastFrameSeen) and occupies its feature iff bit 3 is set
+ *     (ORBmatcher.cc:87-89);
+ *   - the second loop (:1167-1180): every point of the slice that is neither seen nor bad goes through
+ *     isInFrustum(pMP, viewing_cos_limit) exactly as orbx_is_in_frustum states it; d_ntomatch[f] =
+ *     nToMatch; d_in_view[f*M + m] (optional) = 1 where it returned true, 0 elsewhere (the host's
+ *     IncreaseVisible);
+ *   - SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:45-129): radius = RadiusByViewingCos
+ *     (> 0.998: 2.5f, else 4.0f), times th when th != 1.0, times mvScaleFactors[level]; levels
+ *     [level - 1, level]; the mvuRight test; TH_HIGH = 100; the ratio test with nnratio; a match
+ *     occupies its feature iff the point's bit 3 is set. Rejected points stay in place as queries with
+ *     an empty window, so the in-order claim resolution sees the points in table order.
+ * Output as for every variant: d_match[f*kp_stride + i], i < d_counts[f], = the table index or -1
+ * (rows past the count are not written); d_nmatches[f] = the reference's return value. A frame with
+ * nToMatch == 0 gets nmatches = 0 and an all -1 row.
+ * Validation on the device: a count above kp_stride is clamped; a d_frame_mp index >= M raises the
+ * ctx's error flag (orbm_check_error) and is treated as none; a d_range pair outside [0, M] or with
+ * begin > end raises the flag, and that frame alone gets nmatches = ntomatch = 0 and -1 in its whole
+ * d_match row; a point or pose the isInFrustum contract excludes raises the flag and is rejected.
+ * ORBX_EARG for NULL arguments (the table's arrays may be NULL when M == 0), nframes < 0, M < 0,
+ * kp_stride outside [1, 65536], nlevels outside [1, 16], a log_scale_factor that is not finite and > 0,
+ * a non-finite limit, or d_kps_un / d_desc / d_mp_desc not 8- / 16- / 16-byte aligned; nframes == 0 is a
+ * no-op that returns 0. The call only enqueues on `stream` (no upload, no host wait); the ctx's scratch
+ * grows at the first call of a larger nframes x (kp_stride, M) (an allocation: not inside a stream
+ * capture). One ctx serves one stream at a time. */
+int orbm_search_local_points_batch_device(
+    orbm_ctx* ctx, int nframes, const orbx_kp* d_kps_un, const uint8_t* d_desc, const int32_t* d_counts,
+    int kp_stride, const float* d_uright, const float* d_Tcw, const orbm_track_geom* geom,
+    float log_scale_factor, int M, const float* d_pos, const float* d_normal, const float* d_min_dist,
+    const float* d_max_dist, const uint8_t* d_mp_desc, const uint8_t* d_mp_flags, const int32_t* d_range,
+    const int32_t* d_frame_mp, float th, float nnratio, float viewing_cos_limit, int32_t* d_match,
+    int32_t* d_nmatches, int32_t* d_ntomatch, uint8_t* d_in_view, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Synthetic input: deterministic frame t of agent a, width x height,
  * written to host out (pitch = width). Identical on every machine (integer-only).
  * ---------------------------------------------------------------------------------- */

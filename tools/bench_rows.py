@@ -32,6 +32,13 @@
                pairs in one launch (orbm_search_by_projection_last_frame_batch_device), each alone from HIP events
                (median of five windows, min-max), vs the per-call orbm_search_by_projection_last_frame over the same
                pairs from host arrays (wall clock around the calls); the two must agree on every pair.
+  local        Local-map tracking on C2's shape: a 256-frame stereo batch resident in HBM and a local map of M = 4096
+               MapPoints (the unprojected stereo keypoints of frames spread over the batch), Tracking::SearchLocalPoints
+               of every frame in one launch (orbm_search_local_points_batch_device: marks, isInFrustum, search) and
+               Frame::isInFrustum of the table under every pose alone (orbx_is_in_frustum_batch_device), from HIP events
+               (median of five windows, min-max), vs the only route without them: the host unit orbx_is_in_frustum per
+               frame, then the per-call orbm_search_by_projection_local from host arrays (wall clock around each); the
+               two routes must agree on every frame.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -566,6 +573,122 @@ def bench_track(torch, reps, B=1280):
     return row
 
 
+def bench_local(torch, reps, B=256, M=4096):
+    import orbamd
+    from orbamd.device import STEREO_RIGS, BatchPipeline
+    from orbamd.frame import is_in_frustum
+    W, H = 640, 480
+    rig = STEREO_RIGS["euroc"]
+    pipe = BatchPipeline(torch, W, H, B, nfeatures=1000, stereo=rig)
+    dev, S = pipe.dev, pipe.stride
+    left = orbamd.synth_frames(0, 0, B, W, H)
+    right = orbamd.synth_frames(0, 0, B, W, H, dx=8)
+    pipe.extract(torch.from_numpy(np.concatenate([left, right])).to(dev))
+    torch.cuda.synchronize()
+    pipe.check_error()
+    rng = np.random.default_rng(1)
+    poses = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    poses[:, :3, 3] = np.cumsum(rng.normal(0, 0.0005, (B, 3)), 0).astype(np.float32)  # a slow drift
+    tposes = torch.from_numpy(poses).to(dev)
+    flags = torch.zeros((B, S), dtype=torch.uint8, device=dev)
+    pos = pipe.unproject(tposes, mp_flags=flags)
+    torch.cuda.synchronize()
+    # the local map, built on the host (not timed): the keypoints with depth of frames spread over the batch, until M
+    counts = pipe.counts[:B].cpu().numpy()
+    kall = pipe.kps_un[:B].cpu().numpy().copy().view(np.uint8).view(orbamd.kp_dtype).reshape(B, S)
+    dall, uall = pipe.desc[:B].cpu().numpy(), pipe.uright.cpu().numpy()
+    pall, fall = pos.cpu().numpy(), flags.cpu().numpy()
+    scale = np.asarray(pipe.scale, np.float32)
+    tp, tn, tmin, tmax, td = [], [], [], [], []
+    have = 0
+    for f in ((i * 37) % B for i in range(B)):
+        n = int(counts[f])
+        ok = fall[f, :n] != 0
+        P = pall[f, :n][ok]
+        Ow = -(poses[f, :3, :3].astype(np.float64).T @ poses[f, :3, 3].astype(np.float64))
+        po = P - Ow
+        dist = np.linalg.norm(po, axis=1)
+        tp.append(P)
+        tn.append((po / dist[:, None]).astype(np.float32))
+        mx = (dist * scale[np.clip(kall[f, :n]["octave"][ok], 0, len(scale) - 1)]).astype(np.float32)
+        tmax.append(mx)
+        tmin.append((mx / scale[-1]).astype(np.float32))
+        td.append(dall[f, :n][ok])
+        have += len(P)
+        if have >= M:
+            break
+    assert have >= M
+    tp, tn, tmin, tmax, td = (np.ascontiguousarray(np.concatenate(a)[:M]) for a in (tp, tn, tmin, tmax, td))
+    tfl = np.full(M, 9, np.uint8)
+    up = lambda a: torch.from_numpy(a).to(dev)  # noqa: E731
+    d_pos, d_nrm, d_min, d_max, d_desc, d_fl = up(tp), up(tn), up(tmin), up(tmax), up(td), up(tfl)
+    frame_mp = torch.full((B, S), -1, dtype=torch.int32, device=dev)
+    out = torch.empty((B, S), dtype=torch.int32, device=dev)
+    nm = torch.zeros(B, dtype=torch.int32, device=dev)
+    ntm = torch.zeros(B, dtype=torch.int32, device=dev)
+    th = 1.0  # Tracking.cc:1185: th = 1 for a stereo camera
+
+    def windows(fn, n):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of n launches: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / n)
+        return float(np.median(times)), min(times), max(times)
+    t_fr = windows(lambda: pipe.frustum(tposes, d_pos, d_nrm, d_min, d_max), reps)
+    t_lo = windows(lambda: pipe.track_local(tposes, d_pos, d_nrm, d_min, d_max, d_desc, d_fl, frame_mp, th, out, nm,
+                                            ntm), reps)
+    pipe.check_match_error()
+    # the route without the batch entries: the host frustum unit per frame, then the per-call search from host arrays
+    g = pipe.track_geom()
+    lsf = pipe.log_scale_factor()
+    views = []
+    for f in range(B):
+        n = int(counts[f])
+        F = orbamd.FrameView(kall[f, :n], dall[f, :n], pipe.scale, W, H, g.fx, g.fy, g.cx, g.cy, bf=g.bf,
+                             uright=uall[f, :n], occupied=np.zeros(n, np.uint8))
+        F.b = np.float32(g.b)
+        views.append(F)
+    mt = orbamd.ORBmatcher(0.8, False)
+
+    def host_route(f):
+        t0 = time.perf_counter()
+        iv, x, y, xr, lv, vc = is_in_frustum(g, lsf, poses[f], tp, tn, tmin, tmax)
+        t1 = time.perf_counter()
+        mps = orbamd.MapPoints(M, desc=td, has_obs=np.ones(M, np.uint8), track_in_view=iv, track_proj_x=x,
+                               track_proj_y=y, track_proj_xr=xr, track_level=lv, track_view_cos=vc)
+        r = mt.SearchByProjectionLocal(views[f], mps, th)
+        return r, int(iv.sum()), t1 - t0, time.perf_counter() - t1
+    for f in range(3):
+        host_route(f)
+    res = [host_route(f) for f in range(B)]
+    mt.close()
+    out_h, nm_h, ntm_h = out.cpu().numpy(), nm.cpu().numpy(), ntm.cpu().numpy()
+    same = all(r[0][0] == nm_h[f] and r[1] == ntm_h[f] and np.array_equal(r[0][1], out_h[f, :len(r[0][1])])
+               for f, r in enumerate(res))
+    t_hf, t_hs = sum(r[2] for r in res), sum(r[3] for r in res)
+    row = {"row": "local", "workload": "C2 640x480 stereo, 1000 feat, %d frames (%.0f keypoints per frame, stride %d), "
+           "local map M = %d points, th %.0f" % (B, counts.sum() / B, S, M, th),
+           "frustum_ms_per_launch": round(t_fr[0], 4), "frustum_ms_min_max": [round(t_fr[1], 4), round(t_fr[2], 4)],
+           "frustum_ns_per_point": round(t_fr[0] * 1e6 / (B * M), 4),
+           "local_ms_per_launch": round(t_lo[0], 4), "local_ms_min_max": [round(t_lo[1], 4), round(t_lo[2], 4)],
+           "local_us_per_frame": round(t_lo[0] * 1e3 / B, 3),
+           "host_frustum_us_per_frame": round(t_hf * 1e6 / B, 2), "per_call_search_us_per_frame": round(t_hs * 1e6 / B, 2),
+           "host_route_us_per_frame": round((t_hf + t_hs) * 1e6 / B, 2),
+           "in_view_per_frame": round(float(ntm_h.mean()), 1), "matches_per_frame": round(float(nm_h.mean()), 1),
+           "batch_equals_host_route": bool(same), "query_compaction": "not measured: rejected points stay in place"}
+    assert same and ntm_h.mean() > M // 4
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -574,7 +697,8 @@ def main():
             "stereo": lambda: bench_stereo(torch, steps), "projection": lambda: bench_projection(50), "fuse": lambda: bench_fuse(50),
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
             "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200),
-            "undistort": lambda: bench_undistort(torch, 200), "track": lambda: bench_track(torch, 10)}
+            "undistort": lambda: bench_undistort(torch, 200), "track": lambda: bench_track(torch, 10),
+            "local": lambda: bench_local(torch, 10)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
