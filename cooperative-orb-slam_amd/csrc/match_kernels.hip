@@ -5,6 +5,9 @@
  *                     (BASELINE "BF"), batch of frame pairs: Hamming distances as a +-1 fp4
  *                     GEMM on the matrix cores, then the reference's selection
  *                     -- ORBmatcher.cc:657-823, 1647-1663.
+ *   k_tri_order       ahead of k_tri_mfma: each pair's queries and candidates ordered along the epipolar
+ *                     pencil, the candidates copied out in that order with a record per 32-candidate tile,
+ *                     so k_tri_mfma skips the tiles off a wave's epipolar band (orb_tri_cull.h).
  *   k_tri_nodes       SearchForTriangulation over common BoW nodes (general form).
  *   k_tri_nodes_pairs the same for a batch of frame pairs, FeatureVectors on the device.
  *   k_bow_pairs       SearchByBoW (KF,F) / (KF,KF) for a batch of frame pairs, FeatureVectors on the device.
@@ -23,6 +26,7 @@
 #include "../../include/orbslam_amd.h"
 #include "orb_match.h"
 #include "orb_match_dev.h"
+#include "orb_tri_cull.h"
 #include "orb_wave.h"
 
 namespace orbamd {
@@ -240,6 +244,296 @@ __device__ __forceinline__ void tri_mfma_body_fp4(const PairSrc& s, const MatchG
     }
 }
 
+/* ----------------------------------------------------------------------------------- */
+/* The same scan over the candidates k_tri_order laid out (orb_tri_cull.h): a candidate     */
+/* passes only within the band of CheckDistEpipolarLine around the query's line, so a wave   */
+/* of 32 queries neighbouring along the epipolar pencil needs few of the 32-candidate tiles  */
+/* of candidates ordered the same way. At workgroup start each wave ballots tri_tile_dead     */
+/* over the pair's tiles (lane half h takes tile 2c + h of chunk c); the chunk loop then runs */
+/* over the chunks some wave needs, and inside a chunk a wave skips the MFMAs and the         */
+/* selection of a tile none of its queries can match in (a wave-uniform branch; every wave    */
+/* meets the barrier). The selection key takes 65535 - original idx2 from the candidate's     */
+/* record: rows of a tile ascend in the original index, so the packed maximum still resolves */
+/* equal distances to the later original candidate, and the minimum over keys does not        */
+/* depend on the order the chunks are visited in. Outputs equal the unculled scan's.          */
+/* ----------------------------------------------------------------------------------- */
+constexpr int kMfMaxChunks = kTriOrdCap / kMfChunk;
+static_assert(kMfMaxChunks <= 64, "the needed-chunk list is compacted by one wave's ballot");
+static_assert(kMfChunk == 2 * kTriTile, "a chunk is two tiles, one per lane half of the cull ballot");
+
+template <bool STEREO>
+__device__ __forceinline__ void tri_mfma_body_cull(const PairSrc& s, const MatchGeom& g, const uint16_t* __restrict__ permQ,
+                                                   const uint8_t* __restrict__ sdesc, const float4* __restrict__ srec,
+                                                   const TriTile* __restrict__ tiles, unsigned long long* stats,
+                                                   int32_t* __restrict__ out, int32_t* __restrict__ nmatch,
+                                                   int only_stereo) {
+    static_assert(kMfWaves == 4 || kMfWaves == 8, "fp4 expansion roles: 4 waves (2 dwords per thread) or 8 (1)");
+    constexpr int kDw = 512 / kMfThreads;
+    __shared__ v4i s_frag[kMfBufs][2][4][64];
+    __shared__ float4 s_rec[kMfBufs][kMfChunk];  // x, y, thf or -1, bits: original idx2 | near-epipole << 16
+    __shared__ float4 s_box[2 * kMfMaxChunks];  // the pair's tile records: xmin, xmax, ymin, ymax
+    __shared__ float s_thf[2 * kMfMaxChunks];   // and the largest threshold (-1: nothing live, or past the last tile)
+    __shared__ uint8_t s_need[kMfWaves][kMfMaxChunks];  // per wave and chunk: bit t = tile t of the chunk is needed
+    __shared__ uint8_t s_list[kMfMaxChunks];            // the chunks some wave needs, ascending
+    __shared__ int s_nlist;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int qblk = blockIdx.x * (32 * kMfWaves);
+    if (qblk >= s.n1) return;  // block-uniform
+    if (s.n2 <= 0) {  // empty candidate frame (block-uniform)
+        if (tid < 32 * kMfWaves && qblk + tid < s.n1) out[permQ[qblk + tid]] = -1;
+        return;
+    }
+    const int h = lane >> 5;
+    const int qpos = qblk + wave * 32 + (lane & 31);
+    const bool qon = qpos < s.n1;
+    const int qi = qon ? (int)permQ[qpos] : 0;
+    const bool st1 = STEREO && qon && s.ur1[qi] >= 0.f;
+    const bool qact = qon && (!STEREO || !only_stereo || st1);
+    v4i bq[4];
+    float la = 0.f, lb = 0.f, lc = 0.f;
+    {
+        const uint4* qd = (const uint4*)(s.desc1 + (long long)qi * 32);
+        const uint4 d0 = qd[0], d1 = qd[1];
+        const uint32_t dw[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+#pragma unroll
+        for (int st = 0; st < 4; st++) bq[st] = fp4_pm1_dword(h ? dw[2 * st + 1] : dw[2 * st]);
+        const orbx_kp k1 = s.kps1[qi];
+        epi_line(g, k1.x, k1.y, &la, &lb, &lc);
+    }
+    // the cull: tile records into LDS, each wave's needed tiles, the workgroup's needed chunks
+    const int ntiles = (s.n2 + kTriTile - 1) / kTriTile, nchunks = (s.n2 + kMfChunk - 1) / kMfChunk;
+    if (tid < 2 * nchunks) {
+        const int tt = min(tid, ntiles - 1);
+        s_box[tid] = *(const float4*)&tiles[tt].xmin;
+        s_thf[tid] = tid < ntiles ? tiles[tt].thf : -1.f;
+    }
+    __syncthreads();
+    for (int c = 0; c < nchunks; c++) {
+        const float4 bx = s_box[2 * c + h];
+        const TriTile tl = {bx.x, bx.y, bx.z, bx.w, s_thf[2 * c + h], 0.f, 0.f, 0.f};
+        const bool alive = qact && !tri_tile_dead(la, lb, lc, tl);
+        const unsigned long long b = __ballot(alive);
+        if (lane == 0) s_need[wave][c] = (uint8_t)(((uint32_t)b != 0u ? 1 : 0) | ((uint32_t)(b >> 32) != 0u ? 2 : 0));
+    }
+    __syncthreads();
+    if (wave == 0) {
+        int any = 0;
+        if (lane < nchunks)
+            for (int w = 0; w < kMfWaves; w++) any |= s_need[w][lane];
+        const unsigned long long m = __ballot(any != 0);
+        if (any) s_list[__popcll(m & ((1ull << lane) - 1ull))] = (uint8_t)lane;
+        if (lane == 0) s_nlist = __popcll(m);
+    }
+    __syncthreads();
+    const int nl = s_nlist;
+    uint32_t best = 0xFFFFFFFFu;
+    const int ec = (tid >> 6) * (64 / kMfWaves) + (tid & 7) + (kDw == 1 ? 0 : 8 * ((tid >> 5) & 1));
+    const int ed = kDw == 1 ? (tid >> 3) & 7 : 2 * ((tid >> 3) & 3);
+    struct DwT { uint32_t w[kDw]; };
+    DwT pd;
+    float4 pr = make_float4(0.f, 0.f, -1.f, 0.f);
+    auto load_chunk = [&](int cb) {
+        const int c = min(cb + ec, s.n2 - 1);
+        pd = *(const DwT*)(sdesc + (long long)c * 32 + 4 * ed);
+        if (tid < kMfChunk) pr = srec[min(cb + tid, s.n2 - 1)];
+    };
+    auto stage = [&](int cbw, int bw) {
+        const bool on = cbw + ec < s.n2;
+        const int tile = ec >> 5, r = ec & 31;
+#pragma unroll
+        for (int k = 0; k < kDw; k++)
+            s_frag[bw][tile][(ed + k) >> 1][32 * ((ed + k) & 1) + r] = fp4_pm1_dword(on ? pd.w[k] : 0u);
+        if (tid < kMfChunk) s_rec[bw][tid] = cbw + tid < s.n2 ? pr : make_float4(0.f, 0.f, -1.0f, 0.f);
+    };
+    int nexec = 0;
+    if (nl > 0) {
+        load_chunk(kMfChunk * s_list[0]);
+        stage(kMfChunk * s_list[0], 0);
+        __syncthreads();
+        if (nl > 1) load_chunk(kMfChunk * s_list[1]);
+    }
+    for (int k = 0, bf = 0; k < nl; k++, bf ^= 1) {
+        if (k + 1 < nl) {
+            stage(kMfChunk * s_list[k + 1], bf ^ 1);
+            if (k + 2 < nl) load_chunk(kMfChunk * s_list[k + 2]);
+        }
+        // the lane's selection over one tile's accumulators (the unculled body's, with the row's record naming idx2)
+        auto select = [&](const v16f& acc, int tile) {
+            auto pk = [&](int rg) { return __float_as_int(acc[rg]) | ((rg & 3) + 8 * (rg >> 2)); };
+            auto dist = [&](int pv) { return (uint32_t)(int)(256.f - __int_as_float(pv & ~31)) >> 1; };
+            int pmax = pk(0);
+#pragma unroll
+            for (int rg = 1; rg < 16; rg++) pmax = max(pmax, pk(rg));
+            uint32_t D = dist(pmax);
+            while (D <= (best >> 16) && D <= 50u) {  // TH_LOW (ORBmatcher.cc:715)
+                const float4 c2 = s_rec[bf][32 * tile + 4 * h + (pmax & 31)];
+                const uint32_t bits = __float_as_uint(c2.w);
+                const uint32_t km = (D << 16) | (65535u - (bits & 0xFFFFu));
+                if (km >= best) break;  // equal distance, an earlier original candidate; the lane's next keys are larger still
+                if ((!STEREO || st1 || (bits >> 16) == 0u) && epi_ok_f(la, lb, lc, c2.x, c2.y, c2.z)) {
+                    best = km;
+                    break;
+                }
+                const int cur = pmax;
+                int nx = INT_MIN;
+#pragma unroll
+                for (int rg = 0; rg < 16; rg++) nx = pk(rg) < cur ? max(nx, pk(rg)) : nx;
+                pmax = nx;
+                D = nx == INT_MIN ? 0xFFFFu : dist(nx);
+            }
+        };
+        const int nb = __builtin_amdgcn_readfirstlane((int)s_need[wave][s_list[k]]);
+        nexec += __popc(nb);
+        // a tile at a time (most waves need one tile of a chunk or none): one accumulator live, the other waves of
+        // the SIMD fill the MFMA chain's latency
+#pragma unroll
+        for (int tile = 0; tile < 2; tile++) {
+            if (!(nb >> tile & 1)) continue;  // wave-uniform
+            v16f acc = (v16f)0.f;
+#pragma unroll
+            for (int st = 0; st < 4; st++)  // cbsz = blgp = 4: fp4 (e2m1) A and B; E8M0 scales 127 = 2^0
+                acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(fp4_operand(s_frag[bf][tile][st][lane]), fp4_operand(bq[st]),
+                                                                      acc, 4, 4, 0, 127, 0, 127);
+            select(acc, tile);
+        }
+        __syncthreads();
+    }
+    best = min(best, (uint32_t)__shfl_xor((int)best, 32, 64));
+    if (qon && h == 0) {
+        const int idx2 = qact && (best >> 16) <= 50u ? (int)(65535u - (best & 0xFFFFu)) : -1;
+        out[qi] = idx2;
+        if (idx2 >= 0) atomicAdd(nmatch, 1);
+    }
+    if (stats && __ballot(qon) != 0ull && lane == 0) {
+        atomicAdd(stats, (unsigned long long)nexec);
+        atomicAdd(stats + 1, (unsigned long long)ntiles);
+    }
+}
+
+/* ----------------------------------------------------------------------------------- */
+/* k_tri_order: one workgroup per pair, ahead of k_tri_mfma on its stream. Queries and      */
+/* candidates are sorted in LDS (bitonic, keys tri_query_key / tri_cand_key << 12 | index:  */
+/* integer keys with the index as tie-break give a permutation whatever the inputs hold);    */
+/* the candidates are cut into 32-candidate tiles, each tile's rows put back in ascending    */
+/* original index (the packed selection resolves equal distances to the later row), and      */
+/* copied out in that order with their records and the tiles' boxes.                         */
+/* ----------------------------------------------------------------------------------- */
+constexpr int kOrdThreads = 512;
+
+/* ascending sort of sa[0 .. npad) and of sb[0 .. npad), npad a power of two, by the whole workgroup: one bitonic
+ * network over both. A step of stride j <= 64 exchanges within the 128 entries the 64 pairs of one wave cover, so
+ * between two such steps the wave's own program order serves (its LDS operations complete in order; the fence keeps
+ * the compiler from moving them); a workgroup barrier stands only around the steps of stride >= 128
+ * (10 instead of 55 at 1024 entries). */
+__device__ __forceinline__ void lds_sort2_u32(uint32_t* sa, uint32_t* sb, int npad) {
+    bool wide_prev = true;  // the entries were filled by other waves
+    for (int k = 2; k <= npad; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            const bool wide = j >= 128;
+            if (wide || wide_prev) __syncthreads();
+            else __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            wide_prev = wide;
+            for (int i = threadIdx.x; i < (npad >> 1); i += kOrdThreads) {
+                const int lo = ((i & ~(j - 1)) << 1) | (i & (j - 1)), hi = lo | j;
+                const bool up = (lo & k) == 0;
+                const uint32_t a = sa[lo], b = sa[hi], c = sb[lo], d = sb[hi];
+                if ((a > b) == up) {
+                    sa[lo] = b;
+                    sa[hi] = a;
+                }
+                if ((c > d) == up) {
+                    sb[lo] = d;
+                    sb[hi] = c;
+                }
+            }
+        }
+    __syncthreads();
+}
+
+template <bool STEREO>
+__global__ __launch_bounds__(kOrdThreads) void k_tri_order(const int32_t* __restrict__ q1, const int32_t* __restrict__ q2,
+                                                           const orbx_kp* __restrict__ kps, const uint8_t* __restrict__ desc,
+                                                           const int32_t* __restrict__ counts,
+                                                           const float* __restrict__ uright, int kp_stride, MatchGeom g,
+                                                           int only_stereo, TriPlan pl) {
+    __shared__ uint32_t s_kq[kTriOrdCap], s_key[kTriOrdCap];  // query keys, candidate keys
+    __shared__ uint16_t s_perm[kTriOrdCap];
+    constexpr uint32_t kIdxMask = kTriOrdCap - 1;
+    const int p = blockIdx.x, tid = threadIdx.x;
+    const int f1 = q1[p], f2 = q2[p];
+    const int cap = min(kp_stride, min(pl.S, kTriOrdCap));
+    const int n1 = min(max(counts[f1], 0), cap), n2 = min(max(counts[f2], 0), cap);
+    const orbx_kp* k1 = kps + (long long)f1 * kp_stride;
+    const orbx_kp* k2 = kps + (long long)f2 * kp_stride;
+    const uint8_t* d2 = desc + (long long)f2 * kp_stride * 32;
+    const TriOrd o = tri_ord_make(g.F);
+    const long long row = (long long)p * pl.S;
+
+    int npad = 1;
+    while (npad < max(n1, n2)) npad <<= 1;
+    for (int i = tid; i < npad; i += kOrdThreads) {
+        uint32_t kq = 0xFFFFFFFFu, kc = 0xFFFFFFFFu;
+        if (i < n1) {
+            const orbx_kp kp = k1[i];
+            float a, b, c;
+            epi_line(g, kp.x, kp.y, &a, &b, &c);
+            kq = tri_query_key(o, a, b, c) << kTriOrdIdxBits | (uint32_t)i;
+        }
+        if (i < n2) {
+            const orbx_kp kp = k2[i];
+            kc = tri_cand_key(o, kp.x, kp.y) << kTriOrdIdxBits | (uint32_t)i;
+        }
+        s_kq[i] = kq;
+        s_key[i] = kc;
+    }
+    lds_sort2_u32(s_kq, s_key, npad);
+    for (int i = tid; i < n1; i += kOrdThreads) pl.permQ[row + i] = (uint16_t)(s_kq[i] & kIdxMask);
+    for (int i = tid; i < n2; i += kOrdThreads) {  // rows of a tile: ascending original index
+        const int tb = i & ~(kTriTile - 1), cnt = min(kTriTile, n2 - tb);
+        const uint32_t my = s_key[i] & kIdxMask;
+        int r = 0;
+        for (int k = 0; k < cnt; k++) r += (s_key[tb + k] & kIdxMask) < my;
+        s_perm[tb + r] = (uint16_t)my;
+    }
+    __syncthreads();
+    for (int base = 0; base < n2; base += kOrdThreads) {  // a tile = one lane half; every lane takes part in the shuffles
+        const int i = base + tid;
+        const bool on = i < n2;
+        float x = 0.f, y = 0.f, thf = -1.f;
+        if (on) {
+            const int j = s_perm[i];
+            const orbx_kp kp = k2[j];
+            x = kp.x;
+            y = kp.y;
+            uint32_t near = 0u;
+            if (STEREO) {
+                const bool st2 = uright[(long long)f2 * kp_stride + j] >= 0.f;  // bStereo2 (ORBmatcher.cc:727)
+                near = !st2 && near_epipole(g, x, y, kp.octave) ? 1u : 0u;
+                thf = !only_stereo || st2 ? g.th384f[kp.octave] : -1.f;
+            } else {
+                thf = near_epipole(g, x, y, kp.octave) ? -1.f : g.th384f[kp.octave];
+            }
+            const uint4* sd = (const uint4*)(d2 + (long long)j * 32);
+            uint4* dd = (uint4*)(pl.sdesc + (row + i) * 32);
+            dd[0] = sd[0];
+            dd[1] = sd[1];
+            ((float4*)pl.srec)[row + i] = make_float4(x, y, thf, __uint_as_float((uint32_t)j | near << 16));
+        }
+        const bool live = on && thf >= 0.f;
+        TriTile t = {live ? x : INFINITY, live ? x : -INFINITY, live ? y : INFINITY, live ? y : -INFINITY,
+                     live ? thf : -1.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int w = kTriTile / 2; w > 0; w >>= 1) {
+            t.xmin = fminf(t.xmin, __shfl_xor(t.xmin, w, kTriTile));
+            t.xmax = fmaxf(t.xmax, __shfl_xor(t.xmax, w, kTriTile));
+            t.ymin = fminf(t.ymin, __shfl_xor(t.ymin, w, kTriTile));
+            t.ymax = fmaxf(t.ymax, __shfl_xor(t.ymax, w, kTriTile));
+            t.thf = fmaxf(t.thf, __shfl_xor(t.thf, w, kTriTile));
+        }
+        if (on && (tid & (kTriTile - 1)) == 0) pl.tiles[row / kTriTile + i / kTriTile] = t;
+    }
+}
+
 // 6 waves per SIMD: the compiler fits the kernel in 80 VGPRs (88 unconstrained: 5 waves) without scratch; match-only
 // +19 % (C2 3.50M -> 4.18M pairs/s, 18.2 % -> 21.7 % of the fp4 peak), C2 step +0.5-1 %, C3 +-0, C4 -0.6 %
 // (profiles/r05_ab_match_occupancy.log)
@@ -247,12 +541,13 @@ __device__ __forceinline__ void tri_mfma_body_fp4(const PairSrc& s, const MatchG
 #define ORBX_MF_WPE 6
 #endif
 #define ORBX_MF_ATTR __attribute__((amdgpu_waves_per_eu(ORBX_MF_WPE)))
-template <bool STEREO>
+/* CULL: over k_tri_order's layout pl (the epipolar tile cull); otherwise the full scan, pl unread */
+template <bool STEREO, bool CULL>
 __global__ __launch_bounds__(kMfThreads) ORBX_MF_ATTR void k_tri_mfma(const int32_t* __restrict__ q1, const int32_t* __restrict__ q2,
                                                   const orbx_kp* __restrict__ kps, const uint8_t* __restrict__ desc,
                                                   const int32_t* __restrict__ counts, const float* __restrict__ uright,
                                                   int kp_stride, MatchGeom g, int only_stereo,
-                                                  int32_t* __restrict__ match12, int32_t* __restrict__ nmatches) {
+                                                  int32_t* __restrict__ match12, int32_t* __restrict__ nmatches, TriPlan pl) {
     const int p = blockIdx.y;
     const int f1 = q1[p], f2 = q2[p];
     PairSrc s;
@@ -260,7 +555,17 @@ __global__ __launch_bounds__(kMfThreads) ORBX_MF_ATTR void k_tri_mfma(const int3
     s.kps2 = kps + (long long)f2 * kp_stride; s.desc2 = desc + (long long)f2 * kp_stride * 32; s.n2 = counts[f2];
     s.ur1 = STEREO ? uright + (long long)f1 * kp_stride : nullptr;
     s.ur2 = STEREO ? uright + (long long)f2 * kp_stride : nullptr;
-    tri_mfma_body_fp4<STEREO>(s, g, match12 + (long long)p * kp_stride, nmatches + p, only_stereo);
+    if constexpr (CULL) {
+        const int cap = min(kp_stride, min(pl.S, kTriOrdCap));  // k_tri_order's bound on what it laid out
+        s.n1 = min(s.n1, cap);
+        s.n2 = min(s.n2, cap);
+        const long long row = (long long)p * pl.S;
+        tri_mfma_body_cull<STEREO>(s, g, pl.permQ + row, pl.sdesc + row * 32, (const float4*)pl.srec + row,
+                                   pl.tiles + row / kTriTile, pl.stats, match12 + (long long)p * kp_stride,
+                                   nmatches + p, only_stereo);
+    } else {
+        tri_mfma_body_fp4<STEREO>(s, g, match12 + (long long)p * kp_stride, nmatches + p, only_stereo);
+    }
 }
 
 /* rotation bin of a match: rot = angA[a] - angB[b], (a,b) = (i, j) or, with swap, (j, i) */
@@ -789,15 +1094,29 @@ namespace orbamd {
 
 hipError_t launch_tri_bf(int npairs, const int32_t* q1, const int32_t* q2, const orbx_kp* kps, const uint8_t* desc,
                          const int32_t* counts, int kp_stride, const MatchGeom& g, int32_t* match12,
-                         int32_t* nmatches, hipStream_t st, const float* uright, int only_stereo) {
+                         int32_t* nmatches, hipStream_t st, const float* uright, int only_stereo, const TriPlan* plan) {
     if (npairs == 0) return hipSuccess;
     dim3 grid((kp_stride + 32 * kMfWaves - 1) / (32 * kMfWaves), npairs);
-    if (uright)
-        hipLaunchKernelGGL(k_tri_mfma<true>, grid, dim3(kMfThreads), 0, st, q1, q2, kps, desc, counts, uright, kp_stride,
-                           g, only_stereo, match12, nmatches);
-    else
-        hipLaunchKernelGGL(k_tri_mfma<false>, grid, dim3(kMfThreads), 0, st, q1, q2, kps, desc, counts, uright,
-                           kp_stride, g, 0, match12, nmatches);
+    if (plan && (kp_stride > kTriOrdCap || plan->S < kp_stride || plan->S % kMfChunk)) return hipErrorInvalidValue;
+    const TriPlan pl = plan ? *plan : TriPlan{};
+    if (!uright) only_stereo = 0;
+    if (plan) {
+        if (uright)
+            hipLaunchKernelGGL(k_tri_order<true>, dim3(npairs), dim3(kOrdThreads), 0, st, q1, q2, kps, desc, counts, uright,
+                               kp_stride, g, only_stereo, pl);
+        else
+            hipLaunchKernelGGL(k_tri_order<false>, dim3(npairs), dim3(kOrdThreads), 0, st, q1, q2, kps, desc, counts,
+                               uright, kp_stride, g, only_stereo, pl);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+#define ORBX_TRI_MFMA(ST, CU)                                                                                        \
+    hipLaunchKernelGGL((k_tri_mfma<ST, CU>), grid, dim3(kMfThreads), 0, st, q1, q2, kps, desc, counts, uright, kp_stride, \
+                       g, only_stereo, match12, nmatches, pl)
+    if (uright && plan) ORBX_TRI_MFMA(true, true);
+    else if (uright) ORBX_TRI_MFMA(true, false);
+    else if (plan) ORBX_TRI_MFMA(false, true);
+    else ORBX_TRI_MFMA(false, false);
+#undef ORBX_TRI_MFMA
     return hipGetLastError();
 }
 

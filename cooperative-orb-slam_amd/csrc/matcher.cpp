@@ -145,10 +145,36 @@ void orbm_destroy(orbm_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     c->scratch.release();
+    c->tri_scratch.release();
+    c->tri_stats.release();
     c->err.release();
     if (c->pinned) (void)hipHostFree(c->pinned);
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
+}
+
+/* measurement hooks of the BF triangulation batch calls (orbslam_amd_testing.h) */
+int orbm_debug_tri_cull(orbm_ctx* ctx, int mode) {
+    if (!ctx || mode < 0 || mode > 2) return ORBX_EARG;
+    HIPR(hipSetDevice(ctx->device));
+    if (mode == 2) {
+        if (ctx->tri_stats.ensure(2 * sizeof(unsigned long long))) return ORBX_EDEVICE;
+        HIPR(hipDeviceSynchronize());
+        HIPR(hipMemset(ctx->tri_stats.p, 0, 2 * sizeof(unsigned long long)));
+    }
+    ctx->tri_cull = mode;
+    return 0;
+}
+
+int orbm_debug_tri_cull_counts(orbm_ctx* ctx, unsigned long long out[2]) {
+    if (!ctx || !out) return ORBX_EARG;
+    out[0] = out[1] = 0;
+    if (!ctx->tri_stats.p) return 0;
+    HIPR(hipSetDevice(ctx->device));
+    HIPR(hipDeviceSynchronize());
+    HIPR(hipMemcpy(out, ctx->tri_stats.p, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    HIPR(hipMemset(ctx->tri_stats.p, 0, 2 * sizeof(unsigned long long)));
+    return 0;
 }
 
 /* ORBmatcher::DescriptorDistance (ORBmatcher.cc:1647-1663) -- host scalar */
@@ -524,8 +550,13 @@ int orbm_triangulation_bf_batch_device(orbm_ctx* ctx, int npairs, const int32_t*
     MatchGeom g;
     make_geom(g, F12, ex, ey, nlevels, scale_factors, level_sigma2);
     hipStream_t st = (hipStream_t)stream;
+    TriPlan pl;
+    const bool cull = ctx->tri_culled(kp_stride);
+    if (cull)
+        if (const int rc = ctx->tri_plan(npairs, kp_stride, pl)) return rc;
     HIPR(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t) * npairs, st));
-    HIPR(launch_tri_bf(npairs, d_q1, d_q2, d_kps, d_desc, d_counts, kp_stride, g, d_match12, d_nmatches, st));
+    HIPR(launch_tri_bf(npairs, d_q1, d_q2, d_kps, d_desc, d_counts, kp_stride, g, d_match12, d_nmatches, st, nullptr, 0,
+                       cull ? &pl : nullptr));
     if (check_ori)
         HIPR(launch_rot_filter_pairs(npairs, d_q1, d_q2, d_kps, d_counts, kp_stride, d_match12, d_nmatches, st));
     return 0;
@@ -545,9 +576,13 @@ int orbm_triangulation_bf_stereo_batch_device(orbm_ctx* ctx, int npairs, const i
     MatchGeom g;
     make_geom(g, F12, ex, ey, nlevels, scale_factors, level_sigma2);
     hipStream_t st = (hipStream_t)stream;
+    TriPlan pl;
+    const bool cull = ctx->tri_culled(kp_stride);
+    if (cull)
+        if (const int rc = ctx->tri_plan(npairs, kp_stride, pl)) return rc;
     HIPR(hipMemsetAsync(d_nmatches, 0, sizeof(int32_t) * npairs, st));
     HIPR(launch_tri_bf(npairs, d_q1, d_q2, d_kps, d_desc, d_counts, kp_stride, g, d_match12, d_nmatches, st, d_uright,
-                       only_stereo ? 1 : 0));
+                       only_stereo ? 1 : 0, cull ? &pl : nullptr));
     if (check_ori)
         HIPR(launch_rot_filter_pairs(npairs, d_q1, d_q2, d_kps, d_counts, kp_stride, d_match12, d_nmatches, st));
     return 0;

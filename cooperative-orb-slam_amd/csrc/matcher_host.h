@@ -56,6 +56,29 @@ struct orbm_ctx {
     }
     /* the per-call state words (match_kernels.hip call_tail): ints 16..47 of the zeroed err buffer */
     int32_t* call_state() { return err.as<int32_t>() + 16; }
+    /* The epipolar tile cull of the BF triangulation batch calls (orb_tri_cull.h): k_tri_order's layout for
+     * k_tri_mfma, one row of S entries per pair. Grown here, before the call enqueues anything (an allocation
+     * never lands in a stream capture of the caller's; growing frees the old buffer, which waits for the device).
+     * One buffer per context: the calls that share a context are ordered on one stream (include/orbslam_amd.h).
+     * tri_cull (orbm_debug_tri_cull): 0 = the full scan, 1 = the cull (default), 2 = the cull + tile counters. */
+    orbamd::DevBuf tri_scratch, tri_stats;
+    int tri_cull = 1;
+    bool tri_culled(int kp_stride) const { return tri_cull && kp_stride <= orbamd::kTriOrdCap; }  // else the full scan
+    int tri_plan(int npairs, int kp_stride, orbamd::TriPlan& pl) {
+        orbamd::Carve cv;
+        const size_t S = (size_t)orbamd::align_up(kp_stride, 64), rows = (size_t)npairs * S;
+        const size_t o_perm = cv.take(rows * sizeof(uint16_t)), o_desc = cv.take(rows * 32);
+        const size_t o_rec = cv.take(rows * 16), o_tile = cv.take(rows / orbamd::kTriTile * sizeof(orbamd::TriTile));
+        if (tri_scratch.ensure(cv.off)) return ORBX_EDEVICE;
+        uint8_t* b = tri_scratch.as<uint8_t>();
+        pl.permQ = (uint16_t*)(b + o_perm);
+        pl.sdesc = b + o_desc;
+        pl.srec = (float*)(b + o_rec);
+        pl.tiles = (orbamd::TriTile*)(b + o_tile);
+        pl.stats = tri_cull == 2 ? tri_stats.as<unsigned long long>() : nullptr;
+        pl.S = (int)S;
+        return 0;
+    }
 };
 
 namespace orbamd {

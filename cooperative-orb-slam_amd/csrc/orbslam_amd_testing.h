@@ -56,6 +56,17 @@ int orbx_selftest_sincosf(const float* d_in, float* d_sin, float* d_cos, int n, 
  * floats; an input that is not a positive normal float (outside the restatement's domain) gives a quiet NaN. */
 int orbx_selftest_logf(const float* d_in, float* d_out, int n, void* stream);
 
+/* Measurement hook: which scan subsequent orbm_triangulation_bf_batch_device / _stereo_batch_device calls of this
+ * context run. 0 = the full scan (every candidate tile for every wave); 1 = the epipolar tile cull (k_tri_order, then
+ * k_tri_mfma over its layout; the default, taken whenever kp_stride is within the ordering kernel's capacity); 2 = the
+ * cull, and every wave adds the tiles whose MFMAs it ran and the tiles of its pair to two device counters (zeroed
+ * here). Outputs are identical in every mode. */
+int orbm_debug_tri_cull(orbm_ctx* ctx, int mode);
+
+/* The counters of mode 2 since they were last read: out[0] = tiles executed, out[1] = tiles in all (summed over the
+ * waves that held a query). Waits for the device, then zeroes them. */
+int orbm_debug_tri_cull_counts(orbm_ctx* ctx, unsigned long long out[2]);
+
 #ifdef __cplusplus
 }
 #endif

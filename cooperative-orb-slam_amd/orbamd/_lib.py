@@ -133,6 +133,8 @@ SIGNATURES = {
     "orbx_debug_serial": (_I, [_P, _I]),
     "orbx_debug_alias_frames": (_I, [_P, _I]),
     "orbx_debug_raise_error": (_I, [_P, _I, _P]),
+    "orbm_debug_tri_cull": (_I, [_P, _I]),
+    "orbm_debug_tri_cull_counts": (_I, [_P, _P]),
     "orbm_create": (_I, [_I, C.POINTER(_P)]),
     "orbm_destroy": (None, [_P]),
     "orbm_descriptor_distance": (_I, [_P, _P]),

@@ -199,7 +199,11 @@ int orbm_search_by_bow_kf_kf(orbm_ctx* ctx, const orbm_kf_view* kf1, const orbm_
  * output (kps/desc/counts/kp_stride as produced there). All keypoints monocular, no
  * MapPoints, one F12/(ex,ey) and one scale table for all pairs. match12[p*kp_stride+i]; only
  * rows i < counts[q1[p]] are written. kp_stride <= 65536 (ORBX_EARG above it, here and in the
- * stereo form: the kernel's selection key holds the candidate index in 16 bits). */
+ * stereo form: the kernel's selection key holds the candidate index in 16 bits).
+ * This call and the stereo form keep per-launch scratch in the context (the pairs' queries and
+ * candidates ordered along the epipolar lines, for kp_stride <= 4096; grown before anything is
+ * enqueued, when a launch is larger than any before it): calls that share a context must be
+ * ordered on one stream. A context of its own per stream lifts that. */
 int orbm_triangulation_bf_batch_device(orbm_ctx* ctx, int npairs, const int32_t* d_q1,
                                        const int32_t* d_q2, const orbx_kp* d_kps,
                                        const uint8_t* d_desc, const int32_t* d_counts,
