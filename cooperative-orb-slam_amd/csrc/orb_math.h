@@ -13,6 +13,10 @@
  *  - glibc_logf: the float log of MapPoint::PredictScale (MapPoint.cc:385-417, inside Frame::isInFrustum). Restated
  *    from glibc 2.35's logf (sysdeps/ieee754/flt-32/e_logf.c), constants read from libm's __logf_data. Verified
  *    equal to the host libm for every positive normal float (tools/check_logf.c).
+ *  - glibc_atan2f: the float atan2 of cosParallaxStereo in LocalMapping::CreateNewMapPoints (LocalMapping.cc:312), first
+ *    quadrant only. Restated from glibc 2.35's atanf / atan2f (s_atanf.c, e_atan2f.c, the fdlibm float forms), all in
+ *    float. Verified equal to the host libm on every third positive finite float and on 8.4e6 first-quadrant pairs
+ *    (tools/check_atan2f.c).
  *  - fast_atan2: cv::fastAtan2 (OpenCV 3.x scalar form), called by IC_Angle
  *    (ORBextractor.cc:103).
  */
@@ -143,6 +147,72 @@ __device__ __forceinline__ float glibc_logf(float x) {
     y = __dadd_rn(__dmul_rn(LOGF_A0, r2), y);
     y = __dadd_rn(__dmul_rn(y, r2), __dadd_rn(y0, r));
     return __double2float_rn(y);
+}
+
+/* glibc 2.35 atanf (sysdeps/ieee754/flt-32/s_atanf.c, the fdlibm float form) for x >= 0: break points 0.4375, 0.6875,
+ * 1.1875, 2.4375, the atanhi / atanlo tables and the 11-term aT polynomial split into odd and even parts, every
+ * operation in float without contraction. x below 2^-29 returns x; x at or above 2^25 returns atanhi[3] + atanlo[3].
+ * tools/check_atan2f.c states the same sequence in C and compares it with the host libm. */
+__device__ __forceinline__ float glibc_atanf_pos(float x) {
+    const uint32_t ix = __float_as_uint(x);
+    const float hi3 = __uint_as_float(0x3fc90fdau), lo3 = __uint_as_float(0x33a22168u);
+    if (ix >= 0x4c000000u) return __fadd_rn(hi3, lo3);
+    int id = -1;
+    if (ix < 0x3ee00000u) {
+        if (ix < 0x31000000u) return x;
+    } else if (ix < 0x3f980000u) {
+        if (ix < 0x3f300000u) {
+            id = 0;
+            x = __fdiv_rn(__fsub_rn(__fmul_rn(2.0f, x), 1.0f), __fadd_rn(2.0f, x));
+        } else {
+            id = 1;
+            x = __fdiv_rn(__fsub_rn(x, 1.0f), __fadd_rn(x, 1.0f));
+        }
+    } else if (ix < 0x401c0000u) {
+        id = 2;
+        x = __fdiv_rn(__fsub_rn(x, 1.5f), __fadd_rn(1.0f, __fmul_rn(1.5f, x)));
+    } else {
+        id = 3;
+        x = __fdiv_rn(-1.0f, x);
+    }
+    const float aT0 = __uint_as_float(0x3eaaaaabu), aT1 = __uint_as_float(0xbe4ccccdu),
+                aT2 = __uint_as_float(0x3e124925u), aT3 = __uint_as_float(0xbde38e38u),
+                aT4 = __uint_as_float(0x3dba2e6eu), aT5 = __uint_as_float(0xbd9d8795u),
+                aT6 = __uint_as_float(0x3d886b35u), aT7 = __uint_as_float(0xbd6ef16bu),
+                aT8 = __uint_as_float(0x3d4bda59u), aT9 = __uint_as_float(0xbd15a221u),
+                aT10 = __uint_as_float(0x3c8569d7u);
+    const float z = __fmul_rn(x, x), w = __fmul_rn(z, z);
+    float s1 = __fadd_rn(aT8, __fmul_rn(w, aT10));
+    s1 = __fadd_rn(aT6, __fmul_rn(w, s1));
+    s1 = __fadd_rn(aT4, __fmul_rn(w, s1));
+    s1 = __fadd_rn(aT2, __fmul_rn(w, s1));
+    s1 = __fmul_rn(z, __fadd_rn(aT0, __fmul_rn(w, s1)));
+    float s2 = __fadd_rn(aT7, __fmul_rn(w, aT9));
+    s2 = __fadd_rn(aT5, __fmul_rn(w, s2));
+    s2 = __fadd_rn(aT3, __fmul_rn(w, s2));
+    s2 = __fmul_rn(w, __fadd_rn(aT1, __fmul_rn(w, s2)));
+    const float xs = __fmul_rn(x, __fadd_rn(s1, s2));
+    if (id < 0) return __fsub_rn(x, xs);
+    const float hi = id == 0 ? __uint_as_float(0x3eed6338u) : id == 1 ? __uint_as_float(0x3f490fdau)
+                   : id == 2 ? __uint_as_float(0x3f7b985eu) : hi3;
+    const float lo = id == 0 ? __uint_as_float(0x31ac3769u) : id == 1 ? __uint_as_float(0x33222168u)
+                   : id == 2 ? __uint_as_float(0x33140fb4u) : lo3;
+    return __fsub_rn(hi, __fsub_rn(__fsub_rn(xs, lo), x));
+}
+
+/* y > 0 and x > 0, both finite: the first quadrant, all that cos(2 * atan2(mb / 2, depth)) of CreateNewMapPoints
+ * (LocalMapping.cc:312, :314) needs; anything else is the caller's to exclude */
+__device__ __forceinline__ bool atan2f_domain(float y, float x) {
+    return __float_as_uint(y) - 1u < 0x7f800000u - 1u && __float_as_uint(x) - 1u < 0x7f800000u - 1u;
+}
+/* glibc 2.35 atan2f (e_atan2f.c) in the first quadrant: atanf(y) for x == 1, pi/2 for an exponent gap above 60
+ * (pi_o_2 + 0.5f * pi_lo rounds to pi_o_2), otherwise atanf(fabsf(y / x)) */
+__device__ __forceinline__ float glibc_atan2f(float y, float x) {
+    const int32_t hx = (int32_t)__float_as_uint(x), hy = (int32_t)__float_as_uint(y);
+    if (hx == 0x3f800000) return glibc_atanf_pos(y);
+    const int k = (hy - hx) >> 23;
+    if (k > 60) return __fadd_rn(__uint_as_float(0x3fc90fdbu), __fmul_rn(0.5f, __uint_as_float(0xb3bbbd2eu)));
+    return glibc_atanf_pos(fabsf(__fdiv_rn(y, x)));
 }
 
 }  // namespace orbamd

@@ -56,6 +56,11 @@ int orbx_selftest_sincosf(const float* d_in, float* d_sin, float* d_cos, int n, 
  * floats; an input that is not a positive normal float (outside the restatement's domain) gives a quiet NaN. */
 int orbx_selftest_logf(const float* d_in, float* d_out, int n, void* stream);
 
+/* Test hook: the device's restatement of glibc atan2f in the first quadrant and of cosParallaxStereo
+ * (LocalMapping.cc:312): d_atan[i] = atan2f(d_y[i], d_x[i]), d_cos[i] = cosf(2 * d_atan[i]) for n device pairs; a pair
+ * that is not positive and finite on both sides (outside the restatement's domain) gives quiet NaNs. */
+int orbx_selftest_atan2f(const float* d_y, const float* d_x, float* d_atan, float* d_cos, int n, void* stream);
+
 /* Measurement hook: which scan subsequent orbm_triangulation_bf_batch_device / _stereo_batch_device calls of this
  * context run. 0 = the full scan (every candidate tile for every wave); 1 = the epipolar tile cull (k_tri_order, then
  * k_tri_mfma over its layout; the default, taken whenever kp_stride is within the ordering kernel's capacity); 2 = the

@@ -41,19 +41,15 @@ __global__ __launch_bounds__(kUnprojectThreads) void k_unproject(float cx, float
     const float2 uv = kps[rec * 3];
     const float z = depth[rec];
     const bool valid = z > 0;
-    float p0 = 0.0f, p1 = 0.0f, p2 = 0.0f;
+    float p[3] = {0.0f, 0.0f, 0.0f};
     if (valid) {
-        const float x = __fmul_rn(__fmul_rn(__fsub_rn(uv.x, cx), z), invfx);
-        const float y = __fmul_rn(__fmul_rn(__fsub_rn(uv.y, cy), z), invfy);
         const float t0 = T[3], t1 = T[7], t2 = T[11];
-        // row i of mRwc = column i of mRcw
-        p0 = gemm_row(T[0], T[4], T[8], x, y, z, gemm_t_neg(T, 0, t0, t1, t2));
-        p1 = gemm_row(T[1], T[5], T[9], x, y, z, gemm_t_neg(T, 1, t0, t1, t2));
-        p2 = gemm_row(T[2], T[6], T[10], x, y, z, gemm_t_neg(T, 2, t0, t1, t2));
+        const float Ow[3] = {gemm_t_neg(T, 0, t0, t1, t2), gemm_t_neg(T, 1, t0, t1, t2), gemm_t_neg(T, 2, t0, t1, t2)};
+        unproject_point(cx, cy, invfx, invfy, T, Ow, uv.x, uv.y, z, p);
     }
-    pos[rec * 3] = p0;
-    pos[rec * 3 + 1] = p1;
-    pos[rec * 3 + 2] = p2;
+    pos[rec * 3] = p[0];
+    pos[rec * 3 + 1] = p[1];
+    pos[rec * 3 + 2] = p[2];
     if (mp_flags) mp_flags[rec] = valid ? (uint8_t)valid_flags : (uint8_t)0;
 }
 

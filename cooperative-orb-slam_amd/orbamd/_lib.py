@@ -41,6 +41,12 @@ class OrbmTrackGeom(C.Structure):
                 [("nlevels", C.c_int32), ("scale_factors", C.c_float * 16)])
 
 
+class OrbmTriGeom(C.Structure):
+    """orbm_tri_geom: what CreateNewMapPoints' per-match loop reads of the two keyframes, one set per call."""
+    _fields_ = ([(k, C.c_float) for k in ("fx", "fy", "cx", "cy", "bf", "b")] +
+                [("nlevels", C.c_int32), ("scale_factors", C.c_float * 16), ("level_sigma2", C.c_float * 16)])
+
+
 class OrbmKfView(C.Structure):
     _fields_ = [("n", C.c_int32), ("desc", C.c_void_p), ("x", C.c_void_p), ("y", C.c_void_p),
                 ("angle", C.c_void_p), ("octave", C.c_void_p), ("uright", C.c_void_p),
@@ -183,6 +189,12 @@ SIGNATURES = {
                                              _P, _P, _P, _P, _P]),
     "orbm_search_local_points_batch_device": (_I, [_P, _I, _P, _P, _P, _I, _P, _P, C.POINTER(OrbmTrackGeom), _F, _I,
                                                    _P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _P, _P, _P, _P, _P]),
+    "orbx_triangulate_matches": (_I, [C.POINTER(OrbmTriGeom), _I, _F, _P, _P, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P,
+                                      _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_I)]),
+    "orbm_create_new_map_points_batch_device": (_I, [_P, _I, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P,
+                                                     C.POINTER(OrbmTriGeom), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                                     _P, _P, _P, _P, _P]),
+    "orbx_selftest_atan2f": (_I, [_P, _P, _P, _P, _I, _P]),
     "orbm_search_by_projection_local": (_I, [_P, _P, _P, _F, _F, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_last_frame": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_keyframe": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),

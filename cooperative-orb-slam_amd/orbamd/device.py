@@ -270,6 +270,54 @@ class BatchPipeline:
             float(nnratio), float(viewing_cos_limit), out.data_ptr(), nmatches.data_ptr(), ntomatch.data_ptr(),
             in_view.data_ptr() if in_view is not None else None, st), "orbm_search_local_points_batch_device")
 
+    # ---- new MapPoints (include/orbslam_amd.h "New MapPoints from triangulation matches") ----
+    def tri_geom(self):
+        """orbm_tri_geom of this pipeline: track_camera(), the stereo rig's mbf / mb (monocular: 0) and the extractor's
+        mvScaleFactors / mvLevelSigma2; both keyframes of every pair use it"""
+        from .frame import tri_geom
+        if getattr(self, "_tri_geom", None) is None:
+            cam = self.track_camera()
+            mbf, mb = self.stereo if self.stereo else (0.0, 0.0)
+            self._tri_geom = tri_geom(cam.fx, cam.fy, cam.cx, cam.cy, mbf, mb, self.scale, self.sigma2)
+        return self._tri_geom
+
+    def create_new_map_points(self, poses, median_depth2=None, match=None, q1=None, q2=None, stream=None):
+        """The per-match loop of LocalMapping::CreateNewMapPoints (LocalMapping.cc:284-450) over the pipeline's own
+        match rows (match_pairs / match_pairs_nodes; pair p = frame q1[p] against q2[p]) on the device: poses float32
+        cuda [B, 4, 4] (mTcw); a monocular pipeline needs median_depth2 float32 cuda [npairs] (KF2's
+        ComputeSceneMedianDepth(2)). Returns a dict of cuda tensors: status int8 [npairs, stride] (ORBM_TRI_*), pos3
+        float32 [npairs, stride, 3], and the table of M = npairs * stride MapPoints track_local reads -- pos, normal
+        [M, 3], min_dist, max_dist [M], desc uint8 [M, 32], flags uint8 [M], feat1, feat2 int32 [M] -- with pair p's
+        new points in rows ranges[p, 0] .. ranges[p, 1] (int32 [npairs, 2], track_local's ranges) and nnew int32
+        [npairs]. Only enqueues; the buffers are allocated once and reused."""
+        torch = self.torch
+        match = self.match if match is None else match
+        q1 = self.q1 if q1 is None else q1
+        q2 = self.q2 if q2 is None else q2
+        P, S = int(q1.numel()), self.stride
+        if not self.stereo and median_depth2 is None:
+            raise RuntimeError("a monocular pipeline needs median_depth2")
+        t = getattr(self, "_new_mp", None)
+        if t is None or t["status"].shape[0] != P:
+            z = lambda *sh, dt=torch.float32: torch.zeros(sh, dtype=dt, device=self.dev)  # noqa: E731
+            t = dict(status=z(P, S, dt=torch.int8), pos3=z(P, S, 3), pos=z(P * S, 3), normal=z(P * S, 3),
+                     min_dist=z(P * S), max_dist=z(P * S), desc=z(P * S, 32, dt=torch.uint8),
+                     flags=z(P * S, dt=torch.uint8), feat1=z(P * S, dt=torch.int32), feat2=z(P * S, dt=torch.int32),
+                     ranges=z(P, 2, dt=torch.int32), nnew=z(P, dt=torch.int32))
+            self._new_mp = t
+        st = self.stream_ptr() if stream is None else stream
+        g = self.tri_geom()
+        check(self.lib.orbm_create_new_map_points_batch_device(
+            self.mh, P, q1.data_ptr(), q2.data_ptr(), self.B, self.kps_un.data_ptr(), self.counts.data_ptr(), S,
+            self.uright.data_ptr() if self.stereo else None, self.depth.data_ptr() if self.stereo else None,
+            self.desc.data_ptr(), poses.data_ptr(), match.data_ptr(), C.byref(g), 0 if self.stereo else 1,
+            median_depth2.data_ptr() if median_depth2 is not None else None, t["status"].data_ptr(),
+            t["pos3"].data_ptr(), t["pos"].data_ptr(), t["normal"].data_ptr(), t["min_dist"].data_ptr(),
+            t["max_dist"].data_ptr(), t["desc"].data_ptr(), t["flags"].data_ptr(), t["feat1"].data_ptr(),
+            t["feat2"].data_ptr(), t["ranges"].data_ptr(), t["nnew"].data_ptr(), st),
+            "orbm_create_new_map_points_batch_device")
+        return t
+
     def step(self, frames, stream=None):
         self.extract(frames, stream)
         self.match_pairs(stream)

@@ -18,7 +18,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import KP_FIELDS, OrbmTrackGeom, OrbxCamera, check, load
+from ._lib import KP_FIELDS, OrbmTrackGeom, OrbmTriGeom, OrbxCamera, check, load
 
 
 def compute_stereo_matches(left, right, kpsL, descL, kpsR, descR, mbf, mb):
@@ -131,6 +131,63 @@ def track_geom(fx, fy, cx, cy, bf, b, bounds, grid_w_inv, grid_h_inv, scale_fact
     for i, v in enumerate(s):
         g.scale_factors[i] = float(v)
     return g
+
+
+def tri_geom(fx, fy, cx, cy, bf, b, scale_factors, level_sigma2):
+    """orbm_tri_geom: camera, mbf, mb, mvScaleFactors and mvLevelSigma2 (1 to 16 levels) of both keyframes."""
+    s = np.asarray(scale_factors, np.float32)
+    q = np.asarray(level_sigma2, np.float32)
+    if not 1 <= len(s) <= 16 or len(q) != len(s):
+        raise ValueError("1 to 16 scale factors and as many sigma2")
+    g = OrbmTriGeom()
+    g.fx, g.fy, g.cx, g.cy, g.bf, g.b = (float(np.float32(v)) for v in (fx, fy, cx, cy, bf, b))
+    g.nlevels = len(s)
+    for i in range(len(s)):
+        g.scale_factors[i], g.level_sigma2[i] = float(s[i]), float(q[i])
+    return g
+
+
+class NewMapPoints:
+    """what orbx_triangulate_matches writes for one pair: status int8 [n1] (ORBM_TRI_*), pos3 float32 [n1, 3], and
+    the nnew new MapPoints in idx1 order: tab_pos, tab_normal [nnew, 3], tab_min, tab_max [nnew], tab_desc uint8
+    [nnew, 32], tab_flags uint8 [nnew], feat1, feat2 int32 [nnew]"""
+    FIELDS = ("status", "pos3", "tab_pos", "tab_normal", "tab_min", "tab_max", "tab_desc", "tab_flags", "feat1",
+              "feat2")
+
+
+def triangulate_matches(geom, monocular, median_depth2, Tcw1, Tcw2, kps1, uright1, depth1, desc1, kps2, uright2,
+                        depth2, match12):
+    """The per-match body of LocalMapping::CreateNewMapPoints (LocalMapping.cc:284-450, with the baseline test of
+    :244-261 and MapPoint::UpdateNormalAndDepth) for one pair on the host: geom = an orbm_tri_geom (tri_geom), kps =
+    mvKeysUn (structured arrays of kp_dtype), uright / depth = mvuRight / mvDepth float32 or None (monocular), desc1
+    uint8 [n1, 32], match12 int32 [n1] = idx2 or negative. Returns a NewMapPoints. F12 and the epipole of the matcher
+    before it are orbamd.matcher.compute_f12 / epipole."""
+    kps1 = np.ascontiguousarray(kps1, np.dtype(KP_FIELDS))
+    kps2 = np.ascontiguousarray(kps2, np.dtype(KP_FIELDS))
+    n1, n2 = len(kps1), len(kps2)
+    f = lambda a, n: None if a is None else np.ascontiguousarray(a, np.float32).reshape(n)  # noqa: E731
+    ur1, d1, ur2, d2 = f(uright1, n1), f(depth1, n1), f(uright2, n2), f(depth2, n2)
+    desc1 = np.ascontiguousarray(desc1, np.uint8).reshape(n1, 32)
+    m = np.ascontiguousarray(match12, np.int32).reshape(n1)
+    T1 = np.ascontiguousarray(Tcw1, np.float32).reshape(16)
+    T2 = np.ascontiguousarray(Tcw2, np.float32).reshape(16)
+    r = NewMapPoints()
+    r.status, r.pos3 = np.zeros(n1, np.int8), np.zeros((n1, 3), np.float32)
+    r.tab_pos, r.tab_normal = np.zeros((n1, 3), np.float32), np.zeros((n1, 3), np.float32)
+    r.tab_min, r.tab_max = np.zeros(n1, np.float32), np.zeros(n1, np.float32)
+    r.tab_desc, r.tab_flags = np.zeros((n1, 32), np.uint8), np.zeros(n1, np.uint8)
+    r.feat1, r.feat2 = np.zeros(n1, np.int32), np.zeros(n1, np.int32)
+    nnew = C.c_int(0)
+    p = lambda a: None if a is None else a.ctypes.data  # noqa: E731
+    check(load().orbx_triangulate_matches(
+        C.byref(geom), int(bool(monocular)), float(median_depth2), T1.ctypes.data, T2.ctypes.data, n1, p(kps1), p(ur1),
+        p(d1), p(desc1), n2, p(kps2), p(ur2), p(d2), p(m), p(r.status), p(r.pos3), p(r.tab_pos), p(r.tab_normal),
+        p(r.tab_min), p(r.tab_max), p(r.tab_desc), p(r.tab_flags), p(r.feat1), p(r.feat2), C.byref(nnew)),
+        "orbx_triangulate_matches")
+    r.nnew = nnew.value
+    for k in NewMapPoints.FIELDS[2:]:
+        setattr(r, k, getattr(r, k)[:r.nnew])
+    return r
 
 
 def is_in_frustum(geom, log_scale_factor, Tcw, pos, normal, min_dist, max_dist, viewing_cos_limit=0.5):

@@ -996,6 +996,135 @@ int orbm_search_local_points_batch_device(
     int32_t* d_nmatches, int32_t* d_ntomatch, uint8_t* d_in_view, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * New MapPoints from triangulation matches: the per-match body of
+ * LocalMapping::CreateNewMapPoints (LocalMapping.cc:284-450) with its per-pair baseline test
+ * (:244-261) and MapPoint::UpdateNormalAndDepth (MapPoint.cc:330-371) of the new point's two
+ * observations. Input: the match row of a SearchForTriangulation variant; output: a table of
+ * MapPoints in the row format orbm_search_local_points_batch_device reads.
+ * ---------------------------------------------------------------------------------- */
+
+/* What the loop reads of the two keyframes, one set per call. BOTH keyframes use it: the reference
+ * reads each keyframe's own copy (equal within an agent) and even KF1's mbf for KF2 (:406). */
+typedef struct orbm_tri_geom {
+    float fx, fy, cx, cy, bf, b;    /* camera, mbf, mb                                            */
+    int32_t nlevels;                /* mnScaleLevels, 1..16                                       */
+    float scale_factors[16];        /* mvScaleFactors; [1] = mfScaleFactor is read whatever nlevels */
+    float level_sigma2[16];         /* mvLevelSigma2                                              */
+} orbm_tri_geom;
+
+/* One code per outcome of a feature of the current keyframe (status arrays, int8). */
+enum {
+    ORBM_TRI_NO_MATCH = 0,      /* match12[i] < 0                                                   */
+    ORBM_TRI_TRIANGULATED = 1,  /* created by the linear triangulation (:321-338)                   */
+    ORBM_TRI_STEREO1 = 2,       /* created from KF1's stereo (:340-343)                             */
+    ORBM_TRI_STEREO2 = 3,       /* created from KF2's stereo (:344-347)                             */
+    ORBM_TRI_BASELINE = 4,      /* the pair was skipped by the baseline test (:251, :259)           */
+    ORBM_TRI_LOW_PARALLAX = 5,  /* :349                                                             */
+    ORBM_TRI_W_ZERO = 6,        /* :333                                                             */
+    ORBM_TRI_Z1 = 7,            /* :355                                                             */
+    ORBM_TRI_Z2 = 8,            /* :359                                                             */
+    ORBM_TRI_REPROJ1 = 9,       /* :374 / :385                                                      */
+    ORBM_TRI_REPROJ2 = 10,      /* :400 / :411                                                      */
+    ORBM_TRI_DIST_ZERO = 11,    /* :422                                                             */
+    ORBM_TRI_SCALE_RATIO = 12,  /* :430                                                             */
+    ORBM_TRI_EXCLUDED = 13      /* excluded by the contract below                                   */
+};
+
+/* One pair on the host: current keyframe 1 (n1 features: kps1 = mvKeysUn, uright1 / depth1 = mvuRight /
+ * mvDepth or NULL = monocular, all -1; desc1 = mDescriptors), neighbour 2 likewise (no descriptors),
+ * Tcw1 / Tcw2 = their poses (4x4 row-major), match12[i] = idx2 or negative. Pair test: baseline =
+ * (float)sqrt(sum (double)(Ow2 - Ow1)^2), Ow2 - Ow1 in float, Ow = -Rcw.t() * tcw (GEMM_1_T); !monocular:
+ * skipped when baseline < geom->b; monocular: when (double)(baseline / median_depth2) < 0.01, a float
+ * divide (ComputeSceneMedianDepth(2) stays with the caller). Every matched row of a skipped pair gets
+ * ORBM_TRI_BASELINE. The float sequence of one match, in cv::Mat's arithmetic (DESIGN.md "Pinned
+ * semantics"; dot_d / norm_d accumulate (double)a * (double)b from 0 in index order):
+ *   invfx = 1.0f / fx; xn = ((u - cx) * invfx, (v - cy) * invfy, 1) in float, both keyframes;
+ *   ray = Rwc * xn: ray[i] = R[0][i] * xn[0] + R[1][i] * xn[1] + R[2][i] * xn[2], float products summed in
+ *   float (the small-matrix gemm without an addend);
+ *   cosParallaxRays = (float)(dot_d(ray1, ray2) / (norm_d(ray1) * norm_d(ray2)));
+ *   bStereo_k = mvuRight_k >= 0; cosParallaxStereo1 = cosParallaxStereo2 = cosParallaxRays + 1.0f;
+ *   if bStereo1: cosParallaxStereo1 = cosf(2.0f * atan2f(b * 0.5f, depth1)), else if bStereo2 the same for
+ *   KF2 (:311-314, the else kept) -- glibc's float overloads; cosParallaxStereo = std::min(1, 2) = 2 < 1 ? 2 : 1;
+ *   triangulate iff cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0.0f && (bStereo1 || bStereo2 ||
+ *   (double)cosParallaxRays < 0.9998):
+ *     A[0] = xn1[0] * Tcw1.row(2) - Tcw1.row(0), A[1] with xn1[1] and row 1, A[2], A[3] from KF2: a float
+ *     product, then a float difference;
+ *     x = vt.row(3) of cv::SVD::compute(A, w, u, vt, MODIFY_A | FULL_UV), pinned as OpenCV 3.x's built-in
+ *     one-sided Jacobi (no LAPACK) on At = A.t(): W[i] = dot_d(At[i], At[i]), Vt = I; up to 30 sweeps over
+ *     the pairs i < j: p = dot_d(At[i], At[j]); skipped when |p| <= (double)(2 * FLT_EPSILON) * sqrt(W[i] *
+ *     W[j]); p *= 2, beta = W[i] - W[j], gamma = sqrt(p * p + beta * beta) (OpenCV: hypot), all double;
+ *     beta < 0: s = (float)sqrt((gamma - beta) * 0.5 / gamma), c = (float)(p / (gamma * s * 2)); else
+ *     c = (float)sqrt((gamma + beta) / (gamma * 2)), s = (float)(p / (gamma * c * 2)); both rows in float:
+ *     t0 = c * Ai[k] + s * Aj[k], t1 = -s * Ai[k] + c * Aj[k], W[i] and W[j] re-accumulated from t0, t1 in
+ *     double; the same rotation on rows i, j of Vt; stop after a sweep without a rotation; then W[i] =
+ *     sqrt(dot_d(At[i], At[i])) and a selection sort, descending, that swaps W and the rows on strict <;
+ *     x[3] == 0 -> ORBM_TRI_W_ZERO; x3D = x[0..2] * (float)(1.0 / (double)x[3]);
+ *   else if bStereo1 && cosParallaxStereo1 < cosParallaxStereo2: x3D = KF1's orbx_unproject_stereo of idx1;
+ *   else if bStereo2 && cosParallaxStereo2 < cosParallaxStereo1: KF2's of idx2; else ORBM_TRI_LOW_PARALLAX;
+ *   per keyframe: x, y, z = (float)(dot_d(Rcw.row(r), x3D) + (double)tcw[r]); z1 <= 0 -> Z1, then z2 <= 0 -> Z2;
+ *   per keyframe, KF1 first: invz = (float)(1.0 / (double)z); u' = fx * x * invz + cx, v' = fy * y * invz +
+ *   cy (float, left to right); e2 = (u' - u)^2 + (v' - v)^2 in float; with mvuRight: u_r = u' - bf * invz,
+ *   e2 += (u_r - mvuRight)^2 and (double)e2 > 7.8 * (double)sigma2 rejects, without: > 5.991 * sigma2;
+ *   sigma2 = level_sigma2[octave];
+ *   normal_k = x3D - Ow_k (float), dist_k = (float)norm_d(normal_k); dist1 == 0 || dist2 == 0 -> DIST_ZERO;
+ *   ratioDist = dist2 / dist1, ratioOctave = sf[oct1] / sf[oct2], ratioFactor = 1.5f * sf[1]:
+ *   ratioDist * ratioFactor < ratioOctave || ratioDist > ratioOctave * ratioFactor -> SCALE_RATIO;
+ *   the MapPoint: position x3D; normal = ((0.0f + normal1 * (float)(1.0 / norm_d(normal1))) + normal2 *
+ *   (float)(1.0 / norm_d(normal2))) * 0.5f (the norms as doubles; independent of the map order); reference
+ *   keyframe KF1: max_dist = dist1 * sf[oct1], min_dist = max_dist / sf[nlevels - 1] (raw, without the
+ *   0.8f / 1.2f); descriptor = desc1 row idx1 (ComputeDistinctiveDescriptors of two observations has both
+ *   medians 0 and takes the first in std::map<KeyFrame*, ...> order, which is allocator-dependent: pinned
+ *   to the current keyframe); flags = 9 (bit 0 a MapPoint, bit 3 Observations() > 0).
+ * Contract (ORBM_TRI_EXCLUDED, no other row is affected): a non-finite pose entry of either keyframe
+ * (every matched row); idx2 >= n2; an octave outside [0, nlevels); a non-finite keypoint coordinate or
+ * mvuRight; with bStereo1 || bStereo2 a b that is not finite and > 0; a bStereo_k depth that is not finite
+ * and > 0 (only atan2f's first quadrant is restated on the device); a non-finite cosParallaxRays, null
+ * vector, x3D, camera coordinate, e2, dist or ratioDist.
+ * Outputs: status[i], pos3[3i .. +3) (zeros unless created) for every i < n1; the new points in ascending
+ * idx1 order (the reference's creation order) in rows [0, *nnew) of tab_* (each with room for n1 rows;
+ * tab_desc 32 bytes a row; tab_feat1 / tab_feat2 = idx1 / idx2); *nnew = the reference's nnew for this
+ * neighbour. Host only, no device. ORBX_EARG on NULL arguments, n1 < 0, n2 < 0, nlevels outside [1, 16] or
+ * fx == 0 || fy == 0, before anything is written. */
+int orbx_triangulate_matches(const orbm_tri_geom* geom, int monocular, float median_depth2,
+                             const float Tcw1[16], const float Tcw2[16], int n1, const orbx_kp* kps1,
+                             const float* uright1, const float* depth1, const uint8_t* desc1, int n2,
+                             const orbx_kp* kps2, const float* uright2, const float* depth2,
+                             const int32_t* match12, int8_t* status, float* pos3, float* tab_pos,
+                             float* tab_normal, float* tab_min_dist, float* tab_max_dist, uint8_t* tab_desc,
+                             uint8_t* tab_flags, int32_t* tab_feat1, int32_t* tab_feat2, int32_t* nnew);
+
+/* The same for npairs pairs of one device batch, in the batch matchers' layout so that their outputs
+ * plug in unchanged: pair p is current keyframe d_q1[p] against neighbour d_q2[p]; per frame f everything
+ * at f*kp_stride (d_kps_un = mvKeysUn, d_uright / d_depth = mvuRight / mvDepth or both NULL = monocular,
+ * d_desc, count d_counts[f]) and d_Tcw[16 f .. +16); d_match12[p*kp_stride + i] = the matcher's row;
+ * d_median_depth2[p] is read only when monocular != 0 (may be NULL otherwise). Ow is derived per frame on
+ * the device, as orbx_unproject_stereo_batch_device does.
+ * Per feature: d_status[p*kp_stride + i] and d_pos3[(p*kp_stride + i)*3 .. +3); rows i >= d_counts[d_q1[p]]
+ * are not written. Per pair: its new points in ascending idx1 order in rows [p*kp_stride, p*kp_stride +
+ * d_nnew[p]) of d_tab_pos, d_tab_normal (x 3), d_tab_min_dist, d_tab_max_dist, d_tab_desc (x 32, 16-byte
+ * aligned), d_tab_flags, d_tab_feat1, d_tab_feat2 (each npairs*kp_stride rows: a table of M =
+ * npairs*kp_stride MapPoints for orbm_search_local_points_batch_device); d_new_range[2p], [2p+1] =
+ * p*kp_stride, p*kp_stride + d_nnew[p]: a d_range pair usable as-is. Bit-identical to the host form, and
+ * independent of the order or repetition of the pair list.
+ * One launch, one workgroup per pair: the row is walked in chunks of one lane per feature; ballot, prefix
+ * over the waves and a running base give every created point its row, so the compaction keeps idx1 order.
+ * Validation on the device: every ORBM_TRI_EXCLUDED row also raises the ctx's error flag
+ * (orbm_check_error); a pair with a frame index outside [0, nframes) or a count above kp_stride raises it
+ * and gets d_nnew = 0, an empty range and ORBM_TRI_NO_MATCH in its whole d_status row (kp_stride entries;
+ * d_pos3 zeros), and reads nothing out of range; the other pairs are unaffected.
+ * ORBX_EARG before anything is enqueued for NULL arguments, npairs < 0, nframes < 1, kp_stride outside
+ * [1, 65536], nlevels outside [1, 16], fx == 0 || fy == 0, only one of d_uright / d_depth, or d_kps_un /
+ * d_desc / d_tab_desc not 8- / 16- / 16-byte aligned; npairs == 0 (with a valid ctx, geom and sizes) is a
+ * no-op that returns 0. The call only enqueues on `stream`: no upload, no host wait, no scratch. */
+int orbm_create_new_map_points_batch_device(
+    orbm_ctx* ctx, int npairs, const int32_t* d_q1, const int32_t* d_q2, int nframes, const orbx_kp* d_kps_un,
+    const int32_t* d_counts, int kp_stride, const float* d_uright, const float* d_depth, const uint8_t* d_desc,
+    const float* d_Tcw, const int32_t* d_match12, const orbm_tri_geom* geom, int monocular,
+    const float* d_median_depth2, int8_t* d_status, float* d_pos3, float* d_tab_pos, float* d_tab_normal,
+    float* d_tab_min_dist, float* d_tab_max_dist, uint8_t* d_tab_desc, uint8_t* d_tab_flags,
+    int32_t* d_tab_feat1, int32_t* d_tab_feat2, int32_t* d_new_range, int32_t* d_nnew, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Synthetic input: deterministic frame t of agent a, width x height,
  * written to host out (pitch = width). Identical on every machine (integer-only).
  * ---------------------------------------------------------------------------------- */

@@ -39,6 +39,11 @@
                (median of five windows, min-max), vs the only route without them: the host unit orbx_is_in_frustum per
                frame, then the per-call orbm_search_by_projection_local from host arrays (wall clock around each); the
                two routes must agree on every frame.
+  newpoints    New MapPoints on C2's shape: a 256-frame stereo batch 14 pan steps apart, the stereo BF triangulation
+               matcher's rows for the 256 pairs, LocalMapping::CreateNewMapPoints' per-match loop for all pairs in one
+               launch (orbm_create_new_map_points_batch_device) from HIP events (median of five windows, min-max), vs
+               the only route without it: the match rows copied back and the host unit orbx_triangulate_matches per
+               pair (wall clock, median of five); the two must agree on every pair.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -689,6 +694,94 @@ def bench_local(torch, reps, B=256, M=4096):
     return row
 
 
+def bench_newpoints(torch, reps, B=256):
+    """LocalMapping::CreateNewMapPoints' per-match loop for the B pairs of a stereo batch in one launch
+    (orbm_create_new_map_points_batch_device over the stereo BF triangulation matcher's rows), against the only route
+    without it: the match rows copied back and the host unit (orbx_triangulate_matches) per pair."""
+    import orbamd
+    from orbamd.device import STEREO_RIGS, BatchPipeline
+    from orbamd.frame import triangulate_matches
+    from orbamd.matcher import compute_f12, epipole
+    W, H = 640, 480
+    rig = STEREO_RIGS["euroc"]
+    pipe = BatchPipeline(torch, W, H, B, nfeatures=1000, stereo=rig)
+    dev, S = pipe.dev, pipe.stride
+    # frames 14 steps of the synthetic pan apart: a 28 px shift between neighbours, a baseline above the rig's
+    left = np.concatenate([orbamd.synth_frames(0, 14 * f, 1, W, H) for f in range(B)])
+    right = np.concatenate([orbamd.synth_frames(0, 14 * f, 1, W, H, dx=8) for f in range(B)])
+    cam = pipe.track_camera()
+    z = rig[0] / 8.0
+    step = np.array([-28.0 * z / cam.fx, 0.0, -0.002])
+    poses = np.tile(np.eye(4, dtype=np.float32), (B, 1, 1))
+    poses[:, :3, 3] = (np.arange(B)[:, None] * step[None, :]).astype(np.float32)
+    K = np.array([[cam.fx, 0, cam.cx], [0, cam.fy, cam.cy], [0, 0, 1]], np.float32)
+    R = np.eye(3, dtype=np.float32)
+    pipe.F12 = compute_f12(R, poses[1, :3, 3], R, poses[0, :3, 3], K, K)
+    pipe.ex, pipe.ey = epipole(R, poses[0, :3, 3], -poses[1, :3, 3], cam.fx, cam.fy, cam.cx, cam.cy)
+    tposes = torch.from_numpy(poses).to(dev)
+    pipe.extract(torch.from_numpy(np.concatenate([left, right])).to(dev))
+    pipe.match_pairs()
+    torch.cuda.synchronize()
+    pipe.check_error()
+
+    def windows(fn, n):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of n launches: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / n)
+        return float(np.median(times)), min(times), max(times)
+    t_dev = windows(lambda: pipe.create_new_map_points(tposes), reps)
+    t = pipe.create_new_map_points(tposes)
+    torch.cuda.synchronize()
+    pipe.check_match_error()
+    # the route without the batch entry: the match rows back to the host, the host unit per pair
+    g = pipe.tri_geom()
+    counts = pipe.counts[:B].cpu().numpy()
+    kall = pipe.kps_un[:B].cpu().numpy().copy().view(np.uint8).view(orbamd.kp_dtype).reshape(B, S)
+    dall, uall, zall = pipe.desc[:B].cpu().numpy(), pipe.uright.cpu().numpy(), pipe.depth.cpu().numpy()
+    q1, q2 = pipe.q1.cpu().numpy(), pipe.q2.cpu().numpy()
+
+    def host_route():
+        t0 = time.perf_counter()
+        m = pipe.match.cpu().numpy()
+        t1 = time.perf_counter()
+        res = []
+        for p in range(B):
+            a, b = int(q1[p]), int(q2[p])
+            n1, n2 = int(counts[a]), int(counts[b])
+            res.append(triangulate_matches(g, 0, 1.0, poses[a], poses[b], kall[a, :n1], uall[a, :n1], zall[a, :n1],
+                                           dall[a, :n1], kall[b, :n2], uall[b, :n2], zall[b, :n2], m[p, :n1]))
+        return res, t1 - t0, time.perf_counter() - t1
+    host_route()
+    runs = [host_route() for _ in range(5)]
+    t_copy = float(np.median([r[1] for r in runs]))
+    t_host = float(np.median([r[2] for r in runs]))
+    res = runs[-1][0]
+    st, nn, tpos = t["status"].cpu().numpy(), t["nnew"].cpu().numpy(), t["pos"].cpu().numpy()
+    same = all(r.nnew == nn[p] and np.array_equal(r.status, st[p, :len(r.status)]) and
+               r.tab_pos.tobytes() == tpos[p * S:p * S + r.nnew].tobytes() for p, r in enumerate(res))
+    nmatch = float((pipe.match.cpu().numpy() >= 0).sum()) / B
+    row = {"row": "newpoints", "workload": "C2 640x480 stereo, 1000 feat, %d frames (%.0f keypoints per frame, stride "
+           "%d), %d pairs (frame b against b - 1), stereo BF matcher rows" % (B, counts.sum() / B, S, B),
+           "batch_ms_per_launch": round(t_dev[0], 4), "batch_ms_min_max": [round(t_dev[1], 4), round(t_dev[2], 4)],
+           "batch_us_per_pair": round(t_dev[0] * 1e3 / B, 3),
+           "host_copy_us_per_pair": round(t_copy * 1e6 / B, 2), "host_unit_us_per_pair": round(t_host * 1e6 / B, 2),
+           "host_us_per_pair": round((t_copy + t_host) * 1e6 / B, 2),
+           "matches_per_pair": round(nmatch, 1), "new_points_per_pair": round(float(nn.mean()), 1),
+           "batch_equals_host_route": bool(same)}
+    assert same and nn.sum() > 0
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -698,7 +791,7 @@ def main():
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
             "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200),
             "undistort": lambda: bench_undistort(torch, 200), "track": lambda: bench_track(torch, 10),
-            "local": lambda: bench_local(torch, 10)}
+            "local": lambda: bench_local(torch, 10), "newpoints": lambda: bench_newpoints(torch, 10)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
