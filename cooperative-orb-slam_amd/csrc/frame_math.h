@@ -340,4 +340,19 @@ __device__ __forceinline__ int triangulate_match(const orbm_tri_geom& g, const f
     return made;
 }
 
+/* Optimizer::PoseOptimization's double arithmetic (so3_sincos, the SE3 helpers, ldlt6_solve, pose_edge_eval and
+ * Levenberg's bookkeeping): pose_math.h, one statement shared with the host unit pose_optimize.c, here with the
+ * rounding intrinsics. */
+#define PM_DEVICE 1
+#define PM_FN __device__ __forceinline__
+#include "pose_math.h"
+#undef PM_DEVICE
+#undef PM_FN
+#undef PM_UNROLL
+#undef pmM
+#undef pmA
+#undef pmS
+#undef pmD
+#undef pmQ
+
 }  // namespace orbamd

@@ -19,6 +19,8 @@
  *    (tools/check_atan2f.c).
  *  - fast_atan2: cv::fastAtan2 (OpenCV 3.x scalar form), called by IC_Angle
  *    (ORBextractor.cc:103).
+ *  - so3_sincos, the double sin / cos of SE3Quat::exp in Optimizer::PoseOptimization, is not here but in pose_math.h:
+ *    it is the project's own routine, not a restatement of libm's, and is shared with the plain-C host unit.
  */
 #pragma once
 #include <hip/hip_runtime.h>

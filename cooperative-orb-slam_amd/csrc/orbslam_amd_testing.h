@@ -61,6 +61,18 @@ int orbx_selftest_logf(const float* d_in, float* d_out, int n, void* stream);
  * that is not positive and finite on both sides (outside the restatement's domain) gives quiet NaNs. */
 int orbx_selftest_atan2f(const float* d_y, const float* d_x, float* d_atan, float* d_cos, int n, void* stream);
 
+/* Test hooks of the pose optimisation's helpers (pose_math.h), host only: so3_sincos of n doubles; ldlt6_solve of one
+ * symmetric 6x6 system (returns 1, or 0 for a failed solve with x = 0); op 0: state = se3_from_Tcw(Tcw_in), op 1:
+ * state = exp(delta) * se3_from_Tcw(Tcw_in), Tcw_out = se3_to_Tcw(state) either way (returns 1 if exp took its
+ * theta < 0.00001 branch). */
+int orbx_test_so3_sincos(const double* th, double* s, double* c, int n);
+int orbx_test_ldlt6_solve(const double A[36], const double b[6], double x[6]);
+int orbx_test_se3(int op, const float Tcw_in[16], const double delta[6], double state[7], float Tcw_out[16]);
+
+/* Test hook: the device's so3_sincos, correctly rounded double sqrt and 1 / x of n device doubles */
+int orbx_selftest_so3(const double* d_in, double* d_sin, double* d_cos, double* d_sqrt, double* d_rcp, int n,
+                      void* stream);
+
 /* Measurement hook: which scan subsequent orbm_triangulation_bf_batch_device / _stereo_batch_device calls of this
  * context run. 0 = the full scan (every candidate tile for every wave); 1 = the epipolar tile cull (k_tri_order, then
  * k_tri_mfma over its layout; the default, taken whenever kp_stride is within the ordering kernel's capacity); 2 = the

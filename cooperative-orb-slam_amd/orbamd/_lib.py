@@ -195,6 +195,14 @@ SIGNATURES = {
                                                      C.POINTER(OrbmTriGeom), _I, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                                      _P, _P, _P, _P, _P]),
     "orbx_selftest_atan2f": (_I, [_P, _P, _P, _P, _I, _P]),
+    "orbx_pose_optimization": (_I, [C.POINTER(OrbmTrackGeom), _P, _I, _P, _I, _P, _P, _P, _P, _P, C.POINTER(_I),
+                                    C.POINTER(_I), _P]),
+    "orbm_pose_optimization_batch_device": (_I, [_P, _I, _P, _I, _P, _P, _I, _P, C.POINTER(OrbmTrackGeom), _P, _P, _P,
+                                                 _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "orbx_test_so3_sincos": (_I, [_P, _P, _P, _I]),
+    "orbx_test_ldlt6_solve": (_I, [_P, _P, _P]),
+    "orbx_test_se3": (_I, [_I, _P, _P, _P, _P]),
+    "orbx_selftest_so3": (_I, [_P, _P, _P, _P, _P, _I, _P]),
     "orbm_search_by_projection_local": (_I, [_P, _P, _P, _F, _F, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_last_frame": (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),
     "orbm_search_by_projection_keyframe": (_I, [_P, _P, _P, _P, _F, _I, _I, _P, C.POINTER(_I)]),

@@ -318,6 +318,67 @@ class BatchPipeline:
             "orbm_create_new_map_points_batch_device")
         return t
 
+    # ---- pose optimisation (include/orbslam_amd.h "Pose optimisation") ----
+    def inv_level_sigma2(self):
+        """mvInvLevelSigma2 of the pipeline's extractor: 1.0f / mvLevelSigma2[i] (ORBextractor.cc:432)"""
+        return (np.float32(1.0) / np.asarray(self.sigma2, np.float32)).astype(np.float32)
+
+    def optimize_pose(self, poses, pos, mp_index=None, pairs=None, local=None, frames=None, poses_out=None,
+                      mp_flags=None, frame_mp=None, out=None, stream=None):
+        """Optimizer::PoseOptimization (Optimizer.cc:239-451) of one job per entry of frames (int32 cuda [njobs],
+        default frames 0..B-1) over the pipeline's own kps_un, counts and (stereo) uright: poses float32 cuda
+        [B, 4, 4] (mTcw), pos float32 cuda [M, 3] (or [B, stride, 3]) = the MapPoint positions, and each feature's
+        MapPoint as one of
+          mp_index  int32 cuda [njobs, stride]: the row of pos, or negative;
+          pairs     (match, last): a track_pairs result, match[p, i] = the last-frame feature, last int32 [njobs]:
+                    the row is last[p] * stride + match where match >= 0, else -1 (built with torch ops on the stream);
+          local     a track_local result (frame_mp merged with its matches): the row is the entry itself.
+        poses_out (default: poses, in place -- only with the default frames, where job j is frame j) receives the
+        optimised poses. With mp_flags (uint8 [njobs, stride]) bit 2 becomes the outlier flag; with frame_mp (int32
+        [njobs, stride]) an outlier's entry becomes -1 (Tracking's discard loop). Returns a dict of cuda tensors:
+        poses, outlier uint8 [njobs, stride], ninliers, nmatches_map int32 [njobs], status int8 [njobs], mp_index.
+        Only enqueues. Every call returns output tensors of its own, so an earlier result stays valid; out = the dict
+        of an earlier call with the same job count writes into that call's tensors again (a steady-state loop that
+        wants no allocation)."""
+        torch = self.torch
+        S = self.stride
+        st = self.stream_ptr() if stream is None else stream
+        if frames is None:
+            frames = self.q1
+            poses_out = poses if poses_out is None else poses_out
+        elif poses_out is None:
+            raise RuntimeError("a job list of its own needs poses_out")
+        J = int(frames.numel())
+        if pairs is not None:
+            match, last = pairs
+            mp_index = torch.where(match >= 0, last.to(torch.int32).view(-1, 1) * S + match,
+                                   torch.full_like(match, -1)).contiguous()
+        elif local is not None:
+            mp_index = local.contiguous()
+        if mp_index is None:
+            raise RuntimeError("one of mp_index, pairs, local")
+        if frame_mp is True:
+            frame_mp = mp_index.clone()
+        if out is not None:
+            t = dict((k, out[k]) for k in ("outlier", "ninliers", "nmatches_map", "status"))
+            if t["status"].shape[0] != J:
+                raise RuntimeError("out belongs to another job count")
+        else:
+            z = lambda *sh, dt=torch.int32: torch.zeros(sh, dtype=dt, device=self.dev)  # noqa: E731
+            t = dict(outlier=z(J, S, dt=torch.uint8), ninliers=z(J), nmatches_map=z(J), status=z(J, dt=torch.int8))
+        g = self.track_geom()
+        inv = np.zeros(16, np.float32)
+        inv[:len(self.sigma2)] = self.inv_level_sigma2()
+        pos2 = pos.view(-1, 3)
+        check(self.lib.orbm_pose_optimization_batch_device(
+            self.mh, J, frames.data_ptr(), self.B, self.kps_un.data_ptr(), self.counts.data_ptr(), S,
+            self.uright.data_ptr() if self.stereo else None, C.byref(g), inv.ctypes.data, mp_index.data_ptr(),
+            pos2.data_ptr(), int(pos2.shape[0]), poses.data_ptr(), poses_out.data_ptr(), t["outlier"].data_ptr(),
+            mp_flags.data_ptr() if mp_flags is not None else None,
+            frame_mp.data_ptr() if frame_mp is not None else None, t["ninliers"].data_ptr(),
+            t["nmatches_map"].data_ptr(), t["status"].data_ptr(), st), "orbm_pose_optimization_batch_device")
+        return dict(t, poses=poses_out, mp_index=mp_index, frame_mp=frame_mp)
+
     def step(self, frames, stream=None):
         self.extract(frames, stream)
         self.match_pairs(stream)

@@ -209,3 +209,37 @@ def is_in_frustum(geom, log_scale_factor, Tcw, pos, normal, min_dist, max_dist, 
                                     in_view.ctypes.data, x.ctypes.data, y.ctypes.data, xr.ctypes.data,
                                     level.ctypes.data, vc.ctypes.data), "orbx_is_in_frustum")
     return in_view, x, y, xr, level, vc
+
+
+class PoseResult:
+    """what orbx_pose_optimization writes for one frame: Tcw float32 [4, 4], outlier uint8 [n] (mvbOutlier; a feature
+    without a MapPoint keeps the byte it came in with), ninliers, status (ORBM_POSE_*: 0 ok, 1 too few, 2 excluded)
+    and diag int32 [8] (rounds, iterations per round, rejected trials, failed solves, small-angle exps)"""
+
+
+def pose_optimization(geom, inv_level_sigma2, Tcw, kps_un, uright, mp_index, pos, outlier=None):
+    """Optimizer::PoseOptimization (Optimizer.cc:239-451) of one frame on the host: geom = an orbm_track_geom
+    (track_geom; fx, fy, cx, cy, bf are read), inv_level_sigma2 = mvInvLevelSigma2 (1 to 16 floats), Tcw = mTcw 4x4,
+    kps_un = mvKeysUn (kp_dtype), uright = mvuRight float32 [n] or None (monocular), mp_index int32 [n] = the row of
+    each feature's MapPoint in pos (float32 [M, 3]) or negative, outlier = the incoming mvbOutlier (default zeros).
+    Returns a PoseResult."""
+    kps = np.ascontiguousarray(kps_un, np.dtype(KP_FIELDS))
+    n = len(kps)
+    inv = np.ascontiguousarray(inv_level_sigma2, np.float32).reshape(-1)
+    ur = None if uright is None else np.ascontiguousarray(uright, np.float32).reshape(n)
+    mp = np.ascontiguousarray(mp_index, np.int32).reshape(n)
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    r = PoseResult()
+    r.Tcw = np.array(Tcw, np.float32).reshape(16).copy()
+    r.outlier = np.zeros(n, np.uint8) if outlier is None else np.array(outlier, np.uint8).reshape(n).copy()
+    r.diag = np.zeros(8, np.int32)
+    ninl, st = C.c_int(0), C.c_int(0)
+    inv16 = np.zeros(16, np.float32)
+    inv16[:min(len(inv), 16)] = inv[:16]
+    check(load().orbx_pose_optimization(
+        C.byref(geom), inv16.ctypes.data, len(inv), r.Tcw.ctypes.data, n, kps.ctypes.data,
+        None if ur is None else ur.ctypes.data, mp.ctypes.data, pos.ctypes.data, r.outlier.ctypes.data, C.byref(ninl),
+        C.byref(st), r.diag.ctypes.data), "orbx_pose_optimization")
+    r.Tcw = r.Tcw.reshape(4, 4)
+    r.ninliers, r.status = ninl.value, st.value
+    return r

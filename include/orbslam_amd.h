@@ -1125,6 +1125,110 @@ int orbm_create_new_map_points_batch_device(
     int32_t* d_tab_feat1, int32_t* d_tab_feat2, int32_t* d_new_range, int32_t* d_nnew, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Pose optimisation: Optimizer::PoseOptimization(Frame*) (Optimizer.cc:239-451), the one
+ * consumer of every match row the tracking searches write (TrackWithMotionModel,
+ * TrackReferenceKeyFrame, TrackLocalMap, Relocalization).
+ * ---------------------------------------------------------------------------------- */
+enum {
+    ORBM_POSE_OK = 0,       /* optimised: Tcw, outlier and ninliers are the reference's                */
+    ORBM_POSE_TOO_FEW = 1,  /* nInitialCorrespondences < 3 (:364): ninliers = 0, the pose is unchanged */
+    ORBM_POSE_EXCLUDED = 2  /* excluded by the contract below: pose and outlier bytes are unchanged    */
+};
+
+/* PoseOptimization of one frame on the host. g: fx, fy, cx, cy, bf are read; inv_level_sigma2 = mvInvLevelSigma2
+ * (nlevels entries); Tcw = mTcw (row-major 4x4, in and out); kps_un = mvKeysUn, uright = mvuRight (NULL = all
+ * monocular); mp_index[i] = the row of feature i's MapPoint in pos (Mrows x 3, GetWorldPos), negative = none.
+ * Optimizer.cc is followed literally; g2o and Eigen are not part of the reference tree, so their share is pinned
+ * here (DESIGN.md "Pinned semantics"). All arithmetic is double without contraction unless marked.
+ *
+ *   Edges, i ascending over the features with a MapPoint: Xw = (double)pos row; invSigma2 = (double)
+ *   inv_level_sigma2[octave]; uright[i] < 0 -> mono, obs = (x, y), delta = (double)(float)sqrt(5.991); else stereo,
+ *   obs = (x, y, uright[i]), delta = (double)(float)sqrt(7.815). outlier[i] = 0, level 0. Fewer than 3 -> TOO_FEW.
+ *   The active edges of an evaluation are those at level 0, visited in ascending i (mono and stereo interleaved).
+ *
+ *   State (q = (x, y, z, w), t). se3_from_Tcw: R, t widened; tr = R00 + R11 + R22; tr > 0: s = sqrt(tr + 1),
+ *   w = 0.5 s, s = 0.5 / s, x = (R21 - R12) s, y = (R02 - R20) s, z = (R10 - R01) s; else i = argmax of the diagonal
+ *   (first wins; R11 > R00, then R22 > Rii), j, k cyclic: s = sqrt(Rii - Rjj - Rkk + 1), q[i] = 0.5 s, s = 0.5 / s,
+ *   w = (Rkj - Rjk) s, q[j] = (Rji + Rij) s, q[k] = (Rki + Rik) s. Normalise: q /= sqrt(x^2 + y^2 + z^2 + w^2); w < 0
+ *   negates q. se3_map(X) = q (x) X + t with uv = qv x X; uv = uv + uv; (X + w uv) + qv x uv.
+ *   se3_to_Tcw: tx = 2x, ty = 2y, tz = 2z, twx = tx w, twy = ty w, twz = tz w, txx = tx x, txy = ty x, txz = tz x,
+ *   tyy = ty y, tyz = tz y, tzz = tz z; R = [1 - (tyy + tzz), txy - twz, txz + twy; txy + twz, 1 - (txx + tzz),
+ *   tyz - twx; txz - twy, tyz + twx, 1 - (txx + tyy)], each and t cast to float; last row 0 0 0 1.
+ *   se3_exp_mul(d), omega = d[0..3], upsilon = d[3..6]: theta = sqrt(omega . omega), Om = skew(omega), Om2 = Om Om;
+ *   theta < 0.00001: R = (I + Om) + Om2, V = R; else (s, c) = so3_sincos(theta), R = (I + (s / theta) Om) +
+ *   ((1 - c) / (theta theta)) Om2, V = (I + ((1 - c) / (theta theta)) Om) + ((theta - s) / ((theta theta) theta)) Om2;
+ *   qd = quaternion of R (normalised), td = V upsilon; q = normalise(qd (x) q) (Hamilton: w = aw bw - ax bx - ay by
+ *   - az bz, x = aw bx + ax bw + ay bz - az by, y = aw by + ay bw + az bx - ax bz, z = aw bz + az bw + ax by - ay bx),
+ *   t = td + qd (x) t. 3x3 products and sums row-major, left to right.
+ *   so3_sincos: k = (int)(theta (2/pi) + 0.5), r = ((theta - k PIO2_1) - k PIO2_2) - k PIO2_3, Taylor polynomials of degree 17 /
+ *   16 in Horner form, the quadrant from k & 3 (csrc/pose_math.h; not libm's).
+ *
+ *   Edge at the estimate: (X, Y, Z) = se3_map(Xw), invz = 1 / Z, u = (X invz) fx + cx, v = (Y invz) fy + cy, stereo
+ *   ur = u - bf invz; e = obs - (u, v[, ur]); chi2 = sum_r e_r (invSigma2 e_r). Huber while the edge has its kernel:
+ *   chi2 <= delta^2: rho0 = chi2, rho1 = 1; else sq = sqrt(chi2), rho0 = (2 sq) delta - delta^2, rho1 = delta / sq.
+ *   iz2 = invz invz; J row 0 = (((X Y) iz2) fx, -(1 + (X X) iz2) fx, (Y invz) fx, -invz fx, 0, (X iz2) fx), row 1 =
+ *   ((1 + (Y Y) iz2) fy, -((X Y) iz2) fy, -(X invz) fy, 0, -invz fy, (Y iz2) fy), stereo row 2 = (J00 - (bf Y) iz2,
+ *   J01 + (bf X) iz2, J02, J03, 0, J05 - bf iz2). wgt = rho1 invSigma2; H[a][b] += sum_r J[r][a] (wgt J[r][b]) for
+ *   a <= b, mirrored; b[a] += sum_r J[r][a] ((-(invSigma2 e_r)) rho1); the graph's robust chi2 = sum rho0. Inner sums
+ *   over r ascending, the accumulation from 0 over the active edges ascending.
+ *
+ *   Levenberg, one optimize(10): for iter 0..9: evaluate (cur, H, b); iter 0: lambda = 1e-5 max_a |H[a][a]|, nu = 2;
+ *   rho = 0, q = 0; repeat { solve (H + lambda I) x = b by LDL^T without pivoting (d_j = A_jj - sum_{k<j} (L_jk d_k)
+ *   L_jk, a d_j that is not > 0 fails with x = 0; L_ij = (A_ij - sum_{k<j} (L_ik d_k) L_jk) / d_j; y_i = b_i -
+ *   sum_{k<i} L_ik y_k; x_i = y_i / d_i - sum_{k>i} L_ki x_k); save the estimate, apply se3_exp_mul(x), evaluate the
+ *   errors only: tmp = sum rho0, DBL_MAX if the solve failed; scale = sum_a x[a] (lambda x[a] + b[a]) + 1e-3; rho =
+ *   (cur - tmp) / scale; rho > 0 and tmp finite: alpha = min(1 - (2 rho - 1)^3, 2/3), lambda *= max(1/3, alpha), nu
+ *   = 2, cur = tmp; else lambda *= nu, nu *= 2, the saved estimate returns; q++ } while rho < 0 and q < 10. The
+ *   iterations end early when q == 10 or rho == 0.
+ *
+ *   Four rounds (:374-442): the estimate restarts from Tcw, optimize(10) over the active edges (none: no
+ *   iteration); then per edge chi2 = (float) of its error -- an active edge's error is that of the last evaluation
+ *   (after a rejected last trial: at the rejected estimate), an outlier's is recomputed at the estimate -- and
+ *   chi2 > (float)5.991 (mono) / (float)7.815 (stereo) makes it an outlier at level 1, else an inlier at level 0;
+ *   after the third round the Huber kernels are removed; fewer than 10 edges: one round only. Tcw = se3_to_Tcw of the
+ *   last estimate, *ninliers = nInitialCorrespondences - nBad.
+ *
+ * outlier[i] (mvbOutlier) is written for features with a MapPoint only. diag (optional, 8 ints, for tests): rounds
+ * run, the Levenberg iterations of each of the four rounds, rejected trials, failed solves, and exp calls that took
+ * the theta < 0.00001 branch.
+ * Contract (ORBM_POSE_EXCLUDED: *ninliers = 0, Tcw and outlier untouched; the reference's behaviour is undefined or
+ * meaningless there): a non-finite entry of Tcw's first three rows; on a feature with a MapPoint an octave outside
+ * [0, nlevels) or a non-finite keypoint, uright or position; a non-finite robust chi2 at a round's first evaluation.
+ * Host only, no device, no allocation. ORBX_EARG on NULL arguments, n outside [0, 65536] (the kp_stride limit of the
+ * device entries) or nlevels outside [1, 16], before anything is written. */
+int orbx_pose_optimization(const orbm_track_geom* geom, const float* inv_level_sigma2, int nlevels, float Tcw[16],
+                           int n, const orbx_kp* kps_un, const float* uright, const int32_t* mp_index,
+                           const float* pos, uint8_t* outlier, int32_t* ninliers, int32_t* status, int32_t* diag);
+
+/* The same for njobs jobs over one device batch: job j is the reference call on frame d_frame[j] (everything of a
+ * frame at f*kp_stride, count d_counts[f]; d_uright NULL = monocular) with the MapPoints d_mp_index[j*kp_stride + i]
+ * (a row of d_pos, mrows x 3; negative = none) and the pose d_Tcw_in[16 f ..). Jobs share nothing; a frame may appear
+ * in several jobs. Outputs per job: d_Tcw_out[16 j ..) (may alias d_Tcw_in when d_frame[j] == j for every job:
+ * a job reads its pose before it writes it; any other job list needs separate arrays, workgroups are not ordered), d_outlier[j*kp_stride + i] for features with a MapPoint,
+ * d_ninliers[j], d_status[j] (ORBM_POSE_*). Optional, in the same launch:
+ *   d_mp_flags [njobs x kp_stride]   bit 2 := outlier on features with a MapPoint, the other bits kept: the row
+ *                                    orbm_search_by_projection_last_frame_batch_device reads of its LastFrame;
+ *   d_frame_mp [njobs x kp_stride]   Tracking's discard loop (Tracking.cc, after each PoseOptimization): an outlier's
+ *                                    entry becomes -1 (the array orbm_search_local_points_batch_device reads);
+ *   d_nmatches_map [njobs]           nmatchesMap: the kept features whose d_mp_flags bit 3 (Observations() > 0) is set
+ *                                    (without d_mp_flags: all kept features).
+ * One workgroup per job; H, b and the chi2 sums accumulate in double in ascending feature order, so every output is
+ * bit-identical to the host form whatever the schedule.
+ * Validation on the device, each raising the ctx's error flag (orbm_check_error): a count above kp_stride is
+ * clamped; an mp_index >= mrows counts as no MapPoint; a frame index outside [0, nframes) or a row the contract
+ * above excludes gives ORBM_POSE_EXCLUDED with the pose copied through (a bad frame index: d_Tcw_out[16 j ..) is not written), d_ninliers
+ * = 0 and the outlier row, d_mp_flags and d_frame_mp untouched (d_nmatches_map = 0). No job affects another.
+ * ORBX_EARG for NULL required arguments, njobs < 0, nframes < 1, kp_stride outside [1, 65536], mrows < 0, nlevels
+ * outside [1, 16] or d_kps_un not 8-byte aligned; njobs == 0 is a no-op that returns 0. The call only enqueues on
+ * `stream`: no upload, no host wait, no scratch. */
+int orbm_pose_optimization_batch_device(
+    orbm_ctx* ctx, int njobs, const int32_t* d_frame, int nframes, const orbx_kp* d_kps_un, const int32_t* d_counts,
+    int kp_stride, const float* d_uright, const orbm_track_geom* geom, const float* inv_level_sigma2,
+    const int32_t* d_mp_index, const float* d_pos, int mrows, const float* d_Tcw_in, float* d_Tcw_out,
+    uint8_t* d_outlier, uint8_t* d_mp_flags, int32_t* d_frame_mp, int32_t* d_ninliers, int32_t* d_nmatches_map,
+    int8_t* d_status, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Synthetic input: deterministic frame t of agent a, width x height,
  * written to host out (pitch = width). Identical on every machine (integer-only).
  * ---------------------------------------------------------------------------------- */

@@ -44,6 +44,12 @@
                launch (orbm_create_new_map_points_batch_device) from HIP events (median of five windows, min-max), vs
                the only route without it: the match rows copied back and the host unit orbx_triangulate_matches per
                pair (wall clock, median of five); the two must agree on every pair.
+  pose         Pose optimisation on C2's shape: a 256-frame stereo batch resident in HBM, about 300 matched MapPoints
+               per frame (the frame's own stereo keypoints unprojected under its true pose, 5 mm of noise on each
+               position, 5% of them displaced by 0.5 m), a start pose 3 cm and 1 degree off, Optimizer::PoseOptimization
+               of every frame in one launch (orbm_pose_optimization_batch_device) from HIP events (median of five
+               windows, min-max), vs the only route without it: the host unit orbx_pose_optimization per frame from
+               host arrays (wall clock, median of five); the two must agree on every frame, bit for bit.
 The CPU figures are the oracle (a plain-C restatement, 1 thread), not the reference build.
 """
 import json
@@ -782,6 +788,106 @@ def bench_newpoints(torch, reps, B=256):
     return row
 
 
+def bench_pose(torch, reps, B=256, per_frame=300):
+    """Optimizer::PoseOptimization of the B frames of a stereo batch in one launch
+    (orbm_pose_optimization_batch_device), against the only route without it: the host unit (orbx_pose_optimization)
+    per frame over the same arrays read back."""
+    import orbamd
+    from orbamd.device import STEREO_RIGS, BatchPipeline
+    from orbamd.frame import pose_optimization
+    W, H = 640, 480
+    rig = STEREO_RIGS["euroc"]
+    pipe = BatchPipeline(torch, W, H, B, nfeatures=1000, stereo=rig)
+    dev, S = pipe.dev, pipe.stride
+    left = orbamd.synth_frames(0, 0, B, W, H)
+    right = orbamd.synth_frames(0, 0, B, W, H, dx=8)
+    cam = pipe.track_camera()
+    z = rig[0] / 8.0
+    rng = np.random.default_rng(11)
+    true = np.tile(np.eye(4, dtype=np.float64), (B, 1, 1))
+    true[:, 0, 3] = -2.0 * z / cam.fx * np.arange(B)
+    start = np.empty((B, 4, 4), np.float32)
+    for f in range(B):
+        ax = rng.normal(size=3)
+        ax /= np.linalg.norm(ax)
+        K = np.array([[0, -ax[2], ax[1]], [ax[2], 0, -ax[0]], [-ax[1], ax[0], 0]])
+        ang = np.radians(1.0)
+        d = np.eye(4)
+        d[:3, :3] = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
+        t = rng.normal(size=3)
+        d[:3, 3] = t / np.linalg.norm(t) * 0.03
+        start[f] = (d @ true[f]).astype(np.float32)
+    ttrue = torch.from_numpy(true.astype(np.float32)).to(dev)
+    tstart = torch.from_numpy(start).to(dev)
+    flags = torch.zeros((B, S), dtype=torch.uint8, device=dev)
+    pipe.extract(torch.from_numpy(np.concatenate([left, right])).to(dev))
+    pos = pipe.unproject(ttrue, mp_flags=flags).clone()
+    valid = flags == 9
+    keep = valid & (torch.cumsum(valid.to(torch.int32), 1) <= per_frame)
+    idx = torch.arange(B * S, dtype=torch.int32, device=dev).view(B, S)
+    mp_index = torch.where(keep, idx, torch.full_like(idx, -1)).contiguous()
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(5)
+    pos += torch.randn(pos.shape, generator=gen, device=dev) * 0.005
+    gross = torch.rand((B, S), generator=gen, device=dev) < 0.05
+    pos[..., 0] += gross.to(torch.float32) * 0.5
+    out = torch.empty_like(tstart)
+    torch.cuda.synchronize()
+    pipe.check_error()
+
+    def windows(fn, n):
+        for _ in range(3):
+            fn()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(5):  # five windows of n launches: the spread goes into the row
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(n):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            times.append(e0.elapsed_time(e1) / n)
+        return float(np.median(times)), min(times), max(times)
+    r = pipe.optimize_pose(tstart, pos, mp_index=mp_index, poses_out=out)
+    run = lambda: pipe.optimize_pose(tstart, pos, mp_index=mp_index, poses_out=out, out=r)  # noqa: E731
+    t_dev = windows(run, reps)
+    r = run()
+    torch.cuda.synchronize()
+    pipe.check_match_error()
+    g, inv = pipe.track_geom(), pipe.inv_level_sigma2()
+    counts = pipe.counts[:B].cpu().numpy()
+    kall = pipe.kps_un[:B].cpu().numpy().copy().view(np.uint8).view(orbamd.kp_dtype).reshape(B, S)
+    uall, mall, hpos = pipe.uright.cpu().numpy(), mp_index.cpu().numpy(), pos.cpu().numpy().reshape(-1, 3)
+
+    def host_route():
+        t0 = time.perf_counter()
+        res = [pose_optimization(g, inv, start[f], kall[f, :counts[f]], uall[f, :counts[f]], mall[f, :counts[f]], hpos)
+               for f in range(B)]
+        return res, time.perf_counter() - t0
+    host_route()
+    runs = [host_route() for _ in range(5)]
+    t_host = float(np.median([x[1] for x in runs]))
+    res = runs[-1][0]
+    hT, ho, hn, hs = (r[k].cpu().numpy() for k in ("poses", "outlier", "ninliers", "status"))
+    same = all(x.Tcw.tobytes() == hT[f].tobytes() and x.ninliers == hn[f] and x.status == hs[f] and
+               np.array_equal(x.outlier[mall[f, :counts[f]] >= 0], ho[f, :counts[f]][mall[f, :counts[f]] >= 0])
+               for f, x in enumerate(res))
+    dg = np.array([x.diag for x in res])
+    err = max(float(np.abs(x.Tcw.astype(np.float64) - true[f]).max()) for f, x in enumerate(res))
+    row = {"row": "pose", "workload": "C2 640x480 stereo, 1000 feat, %d frames (%.0f keypoints per frame, stride %d), "
+           "%.0f matched MapPoints per frame, start 3 cm / 1 deg off" % (B, counts.sum() / B, S, float(keep.sum()) / B),
+           "batch_ms_per_launch": round(t_dev[0], 4), "batch_ms_min_max": [round(t_dev[1], 4), round(t_dev[2], 4)],
+           "batch_us_per_frame": round(t_dev[0] * 1e3 / B, 3), "host_unit_us_per_frame": round(t_host * 1e6 / B, 2),
+           "lm_iterations_per_frame": round(float(dg[:, 1:5].sum(1).mean()), 1),
+           "rejected_trials_per_frame": round(float(dg[:, 5].mean()), 1),
+           "inliers_per_frame": round(float(hn.mean()), 1), "max_pose_error": float("%.3g" % err),
+           "workgroup": "128 lanes, 128-edge chunks (256 not tried)", "batch_equals_host_route": bool(same)}
+    assert same and (hs == 0).all()
+    pipe.close()
+    return row
+
+
 def main():
     import torch
     steps = int(os.environ.get("BENCH_ROWS_STEPS", "10"))
@@ -791,7 +897,8 @@ def main():
             "distinctive": lambda: bench_distinctive(torch, 10), "bow": lambda: bench_bow(torch, 10),
             "tri_nodes": lambda: bench_tri_nodes(torch, 10), "kfdb": lambda: bench_kfdb(torch, 200),
             "undistort": lambda: bench_undistort(torch, 200), "track": lambda: bench_track(torch, 10),
-            "local": lambda: bench_local(torch, 10), "newpoints": lambda: bench_newpoints(torch, 10)}
+            "local": lambda: bench_local(torch, 10), "newpoints": lambda: bench_newpoints(torch, 10),
+            "pose": lambda: bench_pose(torch, 10)}
     for name, fn in rows.items():
         if only and name not in only.split(","):
             continue
