@@ -30,7 +30,7 @@ __global__ __launch_bounds__(256) void k_voc_descend(VocDev v, int levelsup, con
                                                      uint32_t* __restrict__ nid_out) {
     const int f = blockIdx.y;
     const int i = blockIdx.x * 16 + (threadIdx.x >> 4), gl = threadIdx.x & 15, gbase = threadIdx.x & ~15;
-    const int n = counts[f];
+    const int n = min(max(counts[f], 0), stride);  // a count outside [0, stride] stays inside the frame's rows
     if (blockIdx.x * 16 >= n) return;  // block-uniform
     const bool in = i < n;
     const long long fi = (long long)f * stride + (in ? i : 0);
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(kVocThreads) void k_voc_bow(VocDev v, const int32_t
     __shared__ int s_tmp[2 * kVocWaves];
     __shared__ double s_norm;
     const int f = blockIdx.x, tid = threadIdx.x;
-    const int n = counts[f];
+    const int n = min(max(counts[f], 0), stride);  // as k_voc_descend (stride <= kVocMaxFeatures: the sort's capacity)
     const long long fb = (long long)f * stride;
     int n2 = 128;  // the sort's block: 128 keys (padding sorts last)
     while (n2 < n) n2 <<= 1;

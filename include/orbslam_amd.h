@@ -477,7 +477,10 @@ int orbv_transform(orbv_handle* h, const uint8_t* desc, int n, int levelsup, uin
 /* device batch over the frames of an orbx_extract_batch_device output (descriptors at f*kp_stride,
  * d_counts[f]; kp_stride <= 4096): per-feature word id / weight / node id at L-levelsup and per
  * frame the BowVector / FeatureVector (frame f's arrays at f*kp_stride, fv_off at
- * f*(kp_stride+1), counts d_nbow[f], d_nfv[f]). */
+ * f*(kp_stride+1), counts d_nbow[f], d_nfv[f]). A frame's count is read as
+ * min(max(d_counts[f], 0), kp_stride): a negative count is an empty frame, a count above kp_stride
+ * transforms the frame's first kp_stride descriptors, and nothing is read or written outside the
+ * frame's own rows. */
 int orbv_transform_batch_device(orbv_handle* h, int nframes, const uint8_t* d_desc,
                                 const int32_t* d_counts, int kp_stride, int levelsup,
                                 int32_t* d_word, double* d_weight, uint32_t* d_nid,

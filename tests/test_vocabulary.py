@@ -9,6 +9,7 @@ import pytest
 import oracle_py
 import orbamd
 import proj_scenes as ps
+from voc_py import transform_py
 from orbamd.vocabulary import synth_vocabulary, to_text, L1_NORM, L2_NORM, DOT_PRODUCT, TF_IDF, TF, IDF, BINARY
 
 VOCABS = [  # (k, L, seed, ragged, scoring, weighting, levelsup)
@@ -19,61 +20,6 @@ VOCABS = [  # (k, L, seed, ragged, scoring, weighting, levelsup)
     (9, 4, 5, False, L1_NORM, IDF, 2),
     (7, 4, 6, True, DOT_PRODUCT, BINARY, 6),
 ]
-
-
-def transform_py(k, L, scoring, weighting, parent, is_leaf, desc, weight, feats, levelsup):
-    """Pure-Python TemplatedVocabulary::transform (features, BowVector, FeatureVector, levelsup)."""
-    n = len(parent) + 1
-    children = [[] for _ in range(n)]
-    word = [0] * n
-    nw = 0
-    for i in range(1, n):
-        children[parent[i - 1]].append(i)
-        if is_leaf[i - 1] > 0:
-            word[i] = nw
-            nw += 1
-    D = np.concatenate([np.zeros((1, 32), np.uint8), desc])
-    W = np.concatenate([[0.0], weight])
-    bits_nodes = np.unpackbits(D, axis=1)
-    bow, fv = {}, {}
-    must = scoring != DOT_PRODUCT
-    for i, f in enumerate(feats):
-        fb = np.unpackbits(f)
-        nid_level = L - levelsup
-        nid = 0
-        node, level = 0, 0
-        while children[node]:
-            level += 1
-            ch = children[node]
-            d = [int(np.count_nonzero(bits_nodes[c] != fb)) for c in ch]
-            node = ch[int(np.argmin(d))]  # first minimum = `d < best_d` scan
-            if level == nid_level:
-                nid = node
-        w = float(W[node])
-        if w > 0:
-            wid = word[node]
-            if weighting in (TF_IDF, TF):
-                bow[wid] = bow[wid] + w if wid in bow else w
-            else:
-                bow.setdefault(wid, w)
-            fv.setdefault(nid, []).append(i)
-    keys = sorted(bow)
-    vals = [bow[kk] for kk in keys]
-    if weighting in (TF_IDF, TF) and vals and not must:
-        vals = [v / float(len(vals)) for v in vals]
-    if must:
-        if scoring == L2_NORM:
-            norm = 0.0
-            for v in vals:
-                norm += v * v
-            norm = np.sqrt(norm)
-        else:
-            norm = 0.0
-            for v in vals:
-                norm += abs(v)
-        if norm > 0:
-            vals = [v / norm for v in vals]
-    return (np.array(keys, np.uint32), np.array(vals, np.float64)), fv
 
 
 @pytest.mark.parametrize("cfg", VOCABS[:4])
